@@ -32,6 +32,9 @@ Prints ONE JSON line (rank 0) with the contract fields plus
                   first step is also the reference of the metric's ELBO-match condition (`elbo_match`: the HIP path with
                   the oracle's weights, batch, noise and shuffle, every loss term within 1e-4 relative);
   secondary    -- configs[1] measured the same way (N=1 only).
+`--dump-outputs DIR` (e.g. bench_outputs/, which git ignores) also writes what the headline workload's last timed step
+computed as DIR/<name>.npy (dump_outputs): the inputs are seeded, so two builds run with the same arguments can be compared
+output for output.
 """
 import argparse
 import json
@@ -89,7 +92,12 @@ def parse():
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the configs[1] measurement reported as `secondary`")
     ap.add_argument("--timer-kinds", default="fwd,dgrad,wgrad", help="GEMM kinds bracketed with HIP events (fwd,dgrad,wgrad)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline workload's last timed step computed (loss terms, model "
+                         "outputs, updated parameters, gradients) as DIR/<name>.npy (rank 0; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     args.channel_list = WIDE6 if args.channels == "wide6" else [int(c) for c in args.channels.split(",")]
     wl = WORKLOADS[args.workload]
     if args.batch is None:
@@ -233,8 +241,56 @@ def pmc_traffic(kernel, tag):
         return None
 
 
-def run_workload(args, full, B, rank, world, roofline=True):
-    """Times `args.steps` optimizer steps of one workload (after `args.warmup` untimed ones); returns the result fields."""
+DUMP_SAMPLE = 1 << 20    # elements kept of a larger output: a fixed, seeded sample of its flattened elements
+DUMP_LIMIT = 64 << 20    # bytes --dump-outputs may write in all
+
+
+def step_outputs(bl, data_o, model):
+    """name -> tensor: what a caller of the timed step receives -- every loss term, the model's outputs (data_o; None under
+    --graph, whose captured step returns the losses only) and the parameters / gradients the step left in the model.  Scrubber
+    outputs the step never evaluated (lazy entries) are left out."""
+    out = {f"loss_{k}": v for k, v in bl.items() if torch.is_tensor(v)}
+
+    def walk(prefix, v):
+        if torch.is_tensor(v):
+            out[prefix] = v
+        elif isinstance(v, dict):
+            for k, x in v.items():
+                walk(f"{prefix}_{k}", x)
+        elif isinstance(v, (list, tuple)):
+            for i, x in enumerate(v):
+                walk(f"{prefix}_{i}", x)
+    if data_o is not None:
+        walk("out", data_o)
+    out["params"], out["grads"] = model.flat_params, model.flat_grads
+    return out
+
+
+def dump_outputs(path, tensors, sample=DUMP_SAMPLE, limit=DUMP_LIMIT):
+    """Writes every tensor as <path>/<name>.npy, float64 if it is float64 and float32 otherwise.  A tensor with more than `sample`
+    elements is written as the `sample` flattened elements at the sorted positions of torch.randperm(numel) seeded with 0 (the same
+    positions in every run and build).  Returns the bytes written; refuses to write more than `limit`."""
+    import numpy as np
+    arrays = {}
+    for name, t in tensors.items():
+        t = t.detach()
+        if t.numel() > sample:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:sample].sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+        arrays[re.sub(r"[^\w.-]", "_", name)] = a
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit:
+        raise SystemExit(f"--dump-outputs: {total} bytes > the {limit} byte limit")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return total
+
+
+def run_workload(args, full, B, rank, world, roofline=True, dump=None):
+    """Times `args.steps` optimizer steps of one workload (after `args.warmup` untimed ones); returns the result fields.
+    dump: directory that receives what the last timed step computed (dump_outputs), or None."""
     import gc
     gc.collect()  # the previous workload's model (20 GB of buffers at batch 4096) goes back to the allocator before this one builds
     torch.cuda.empty_cache()
@@ -264,6 +320,8 @@ def run_workload(args, full, B, rank, world, roofline=True):
         host = {k: v.cpu().pin_memory() for k, v in data.items()}
         feed = iter(DevicePrefetcher(itertools.repeat(host), "cuda"))
 
+    last = {}
+
     def step():
         if graphed is not None:
             return graphed()
@@ -273,6 +331,8 @@ def run_workload(args, full, B, rank, world, roofline=True):
         bl["total"].backward()
         clip_grad_norm_(model, 1e6)
         opt.step()
+        if dump:
+            last["data_o"] = data_o
         return bl
 
     def barrier():
@@ -304,6 +364,8 @@ def run_workload(args, full, B, rank, world, roofline=True):
     dt = time.perf_counter() - t0
     ov_timed = 0 if args.serial_streams else int(model._ov)  # the stream schedule the K timed steps actually ran (the regions below change it)
     comm_ms = model.pop_comm_times() if world > 1 else []
+    if dump:  # before the roofline region: its steps overwrite the buffers data_o aliases and update the parameters again
+        dump_outputs(dump, step_outputs(bl, last.get("data_o"), model))
     # ---- roofline region: the same K steps again with the side streams serialised and HIP events around every launch of
     # the dominant GEMM template.  In the headline region three HIP streams run kernels concurrently on shared CUs, so a
     # launch's start-to-end time is not the kernel's own time there; serialised, it is.
@@ -456,7 +518,7 @@ def main():
         ones = torch.ones(1, device="cuda" if backend == "nccl" else "cpu")
         torch.distributed.all_reduce(ones)  # every rank contributes 1: the number of ranks the collective really spans
         ranks_seen = int(ones.item())
-    head = run_workload(args, args.full, B, rank, world, roofline=not args.no_roofline)
+    head = run_workload(args, args.full, B, rank, world, roofline=not args.no_roofline, dump=args.dump_outputs if rank == 0 else None)
 
     if rank == 0:
         out = {

@@ -29,6 +29,34 @@ def test_bench_defaults_match_baseline_config():
         sys.argv = old
     assert (a.batch, a.full) == (1024, False)                              # BASELINE configs[1]
     assert a.precision in bench.PRODUCTS
+    assert a.dump_outputs is None
+
+
+def test_dump_outputs_writes_float_arrays_with_a_fixed_sample(tmp_path):
+    """--dump-outputs: small outputs whole, large ones as the same seeded sample of their elements in every run, float32 / float64
+    only, never more than the byte limit."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+
+    import bench
+    big = torch.arange(3 * 1000, dtype=torch.float32).reshape(3, 1000)
+    t = {"loss_total": torch.tensor(2.5), "out_x6d": big, "out_disentangle/k": torch.ones(4, 2, dtype=torch.float16),
+         "d": torch.tensor([1.0], dtype=torch.float64)}
+    n = bench.dump_outputs(str(tmp_path / "a"), t, sample=100)
+    bench.dump_outputs(str(tmp_path / "b"), t, sample=100)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["d.npy", "loss_total.npy", "out_disentangle_k.npy", "out_x6d.npy"]
+    a = {f: np.load(tmp_path / "a" / f) for f in files}
+    assert n == sum(x.nbytes for x in a.values())
+    assert a["loss_total.npy"].dtype == np.float32 and float(a["loss_total.npy"]) == 2.5
+    assert a["d.npy"].dtype == np.float64 and a["out_disentangle_k.npy"].dtype == np.float32
+    s = a["out_x6d.npy"]
+    assert s.shape == (100,) and len(set(s.tolist())) == 100 and np.all(np.diff(s) > 0)   # distinct elements, in flat order
+    assert np.array_equal(s, np.load(tmp_path / "b" / "out_x6d.npy"))
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "c"), t, sample=100, limit=n - 1)
+    assert not os.path.exists(tmp_path / "c")
 
 
 @pytest.mark.gpu
@@ -55,6 +83,36 @@ def test_bench_prints_exactly_one_json_line_with_the_contract_fields():
     c = d["config"]
     assert c["ranks_seen"] == 1 and c["backend"] == "none" and c["bn"] == "single rank"
     assert c["side_streams"] == 0 and c["streams"].startswith("one stream")       # 64 x 64 rows: the serial schedule was timed
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_of_the_last_timed_step(tmp_path):
+    """--dump-outputs writes the last timed step's losses, outputs, parameters and gradients; the same arguments give the same
+    inputs, so two runs agree to fp32 noise, and the dumped total is the loss the JSON line reports."""
+    import numpy as np
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    runs = []
+    for name in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "64",
+                            "--no-cpu-baseline", "--no-roofline", "--dump-outputs", str(tmp_path / name)],
+                           capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        runs.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b"))
+    for f in ("loss_total.npy", "loss_jpe.npy", "out_x6d.npy", "out_mu.npy", "params.npy", "grads.npy"):
+        assert f in files, files
+    a = {f: np.load(tmp_path / "a" / f) for f in files}
+    b = {f: np.load(tmp_path / "b" / f) for f in files}
+    assert all(x.dtype in (np.float32, np.float64) for x in a.values())
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    assert a["out_x6d.npy"].shape == (64, 64, 23, 6)
+    assert float(a["loss_total.npy"]) == runs[0]["config"]["final_total_loss"]
+    for f in files:
+        assert a[f].shape == b[f].shape and np.all(np.isfinite(a[f])), f
+        # fp32 summation-order noise at the array's scale; parameters also tolerate a few Adam steps (lr 1e-4) of sign noise
+        dev = float(np.abs(a[f] - b[f]).max())
+        assert dev <= 1e-3 * float(np.abs(a[f]).max()) + (1e-3 if f == "params.npy" else 0.0), (f, dev)
 
 
 @pytest.mark.gpu
