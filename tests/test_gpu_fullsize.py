@@ -162,3 +162,61 @@ def test_config4_wide_w256_b32_whole_step_vs_oracle(precision):
     default precision and in `bf16x6b3`, under the same gates as configs[1] / configs[2] above."""
     # outputs: 5e-5 as in test_oracle_parity_config5_wide_w256 (six blocks and a 70-tap output conv deep: measured 1.5e-5 / 2.4e-5)
     _run(32, False, precision, seed=61, window=256, channel=WIDE6, expect=("gather_gemm_bf16s_ws_kernel", "wgrad_taps"), out_tol=5e-5)
+
+
+@pytest.mark.parametrize("precision", ["f16x3b3", "bf16x6b3"])
+def test_config4_wide_w256_b1024_step_runs_on_the_tile_table(precision):
+    """BASELINE configs[4] at the benchmark's batch (B = 1024, window 256, six residual blocks to 4096 channels, J = 23, the full SC-VAE
+    heads): one forward, loss, backward and FusedAdam step finds every conv pass in the shipped tile table -- so the per-entry checks of
+    test_gpu_tile_table cover this workload's whole kernel mix -- and runs the 256 x 256 halo and weight-gradient templates the table
+    picks for it.  No oracle at this size: the numbers are checked entry by entry there."""
+    from scrubvae_amd import ops
+    from scrubvae_amd.train.losses import get_batch_loss
+    from scrubvae_amd.train.trainer import FusedAdam, clip_grad_norm_
+    B, seed = 1024, 71
+    feats = ["avg_speed_3d", "heading"]
+    cfg = O.OracleConfig(n_keypts=23, window=256, z_dim=32, kernel=5, diag=True, arena_size=ARENA, kinematic_tree=O.skeleton_tree(23),
+                         method=dict(FULL_METHODS), features=feats, discrete_classes={"ids": torch.arange(4)}, channel=WIDE6)
+    ls = {"jpe": 1.0, "root": 1.0, "prior": 1.0, "avg_speed_3d_gr": 1.0, "heading_gr": 1.0, "heading_an": 1.0}
+    sd = O.init_state_dict(cfg, seed=seed)
+    data = O.synth_batch(cfg, B, seed=seed + 1)
+    g = torch.Generator().manual_seed(seed + 2)
+    eps = torch.randn(B, cfg.z_dim, generator=g)
+    perm = {k: torch.randperm(B, generator=g) for k in cfg.method.get("adversarial_net", [])}
+    keep = ops.PRECISION
+    ops.set_precision(precision)
+    log_before = dict(ops.TUNED_LOG)
+    try:
+        model, dis = build_model(cfg, sd)
+        model.train()
+        model.defer_tail = True
+        opt = FusedAdam(model, lr=LR, weight_decay=0.01, decoupled=True)
+        d = to_dev(data)
+        d["eps"] = eps.cuda()
+        data_o = model(d)
+        bl = get_batch_loss(model, d, data_o, ls, dis, adv_perm=perm)
+        for p in model.parameters():
+            p.grad = None
+        bl["total"].backward()
+        clip_grad_norm_(model, 1e6)
+        torch.cuda.synchronize()
+        grads = {k: v.detach() for k, v in model.grads_state_dict().items()}
+        assert all(bool(torch.isfinite(v).all()) for v in grads.values()), [k for k, v in grads.items() if not torch.isfinite(v).all()]
+        opt.step()
+        torch.cuda.synchronize()
+        ran = [(cv, kind) for cv in model._convs.values() for kind in ("fwd", "dgrad", "wgrad") if kind in cv.__dict__.get("_tuned", ())]
+        names = {cv.kernel_name(kind) for cv, kind in ran}
+        missing = sorted(cv.tile_key(kind) for cv, kind in ran if cv.tile_key(kind) not in ops.TILE_TABLE)
+        params = {k: v for k, v in model.state_dict().items() if v.dtype.is_floating_point}
+    finally:
+        ops.set_precision(keep)
+    assert ops.TUNED_LOG == log_before, sorted(set(ops.TUNED_LOG) - set(log_before))
+    assert not missing, missing
+    assert ran and all(cv.desc.tile[0] != 0 for cv in model._convs.values() if cv.flops >= ops.AUTOTUNE_MIN_FLOPS)
+    for k in bl:
+        assert bool(torch.isfinite(bl[k].detach()).all()), k
+    assert all(bool(torch.isfinite(v).all()) for v in params.values()), [k for k, v in params.items() if not torch.isfinite(v).all()]
+    for e in ("gather_halo_bf16s_kernel<256, 256", "wgrad_gemm_bf16s_kernel<256, 256"):
+        assert any(n.startswith(e) for n in names), (e, sorted(names))
+    print(f"\n[configs[4] B={B} {precision}] {len(ran)} conv passes, {len(names)} kernel instances, all in the tile table; "
+          f"total loss {float(bl['total'].detach()):.6g}")

@@ -10,6 +10,7 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 from oracle import scvae_oracle as O
+from tests.conv_checks import bn_bwd_fused_check
 
 
 @pytest.fixture(scope="module")
@@ -577,38 +578,75 @@ def test_gather_kernel_variants(ops, case, code):
 _SPLIT_TOL = {3: 2e-6, 2: 6e-5, 1: 1.2e-2, 22: 8e-6}  # per sqrt(K): pieces=3 is held to the fp32 kernels' bound; 22 = two fp16 pieces (forward)
 
 
-def _split_cases():
+# Mid-size geometries: 2-4 k output rows that are not multiples of 256 (interior row tiles and a ragged tail of the 256-row
+# templates) and N >= 512 (several column tiles)
+MID_CASES = [
+    # B, L, Cin, Cout, k, stride, pad, transposed
+    (61, 64, 128, 512, 5, 2, 2, False),  # strided: 1952 output rows
+    (93, 32, 512, 512, 5, 1, 2, False),  # 2976 rows
+    (301, 7, 512, 256, 5, 2, 2, True),   # ConvT 7 -> 13: 3913 rows
+    (133, 16, 256, 512, 6, 1, 2, False),  # skip conv (6 taps): 1995 rows
+    (3001, 1, 512, 512, 1, 1, 0, False),  # Linear: 3001 rows
+]
+
+# code lists of the split gather kernels, per pieces
+_SPLIT_GATHER_LISTS = {
+    3: (128128, 64128, 128064, 64064, 1128128, 1064128, 1128064, 1064064, 2128128, 2128064, 3128128, 3128064,
+        4128128, 4128064, 4064128, 5128128, 5128064, 5064128, 5064064,
+        6128128, 6128064, 6064128, 7128128, 7128064, 7064128, 7064064, 8128128, 8128064, 9128128, 9128064,
+        10128128, 10128064, 11128128, 11128064, 12128064, 13128064, 0),
+    2: (64064, 2128064, 3128128, 4128128, 5064064, 8128128, 8128064, 9128128, 9128064,
+        10128128, 10128064, 11128128, 11128064, 12128128, 12128064, 13128128, 13128064, 14128128, 15128128,
+        16128128, 16128064, 17128128, 17128064, 18128128, 18128064, 19128128, 29128128),  # 2 pieces: the backward pass of bf16x6b3
+    1: (1128064,),
+    22: (128128, 1064064, 2128064, 3128128, 4128128, 5064064, 6128064, 7064128, 8128128, 8128064, 9128128, 9128064,
+         10128128, 11128128, 11128064, 12128128, 13128128, 14128128, 15128128,
+         16128128, 16128064, 17128128, 18128128, 18128064, 19128128, 29128128),  # two fp16 pieces / 3 products (the forward of f16x3b3)
+}
+# (pieces, code) pairs the shipped tile table selects that the lists above did not force: data gradients with 2 pieces, forwards
+# with two fp16 pieces (their data gradient runs 2 bf16 pieces on the same code)
+_SPLIT_GATHER_TABLE = {
+    2: (4064128, 3128064, 6128128, 6064128, 2128128, 1064064, 5064128, 7064064),
+    22: (2128128, 17128064, 4064128, 3128064, 5064128, 6064128, 10128064),
+}
+
+
+def _split_cases(cases, lists=_SPLIT_GATHER_LISTS):
     out = []
-    for case in CONV_CASES:
-        for code in (128128, 64128, 128064, 64064, 1128128, 1064128, 1128064, 1064064, 2128128, 2128064, 3128128, 3128064,
-                     4128128, 4128064, 4064128, 5128128, 5128064, 5064128, 5064064,
-                     6128128, 6128064, 6064128, 7128128, 7128064, 7064128, 7064064, 8128128, 8128064, 9128128, 9128064,
-                     10128128, 10128064, 11128128, 11128064, 12128064, 13128064, 0):
-            out.append((case, code, 3))
-        for code in (64064, 2128064, 3128128, 4128128, 5064064, 8128128, 8128064, 9128128, 9128064,
-                     10128128, 10128064, 11128128, 11128064, 12128128, 12128064, 13128128, 13128064, 14128128, 15128128,
-                     16128128, 16128064, 17128128, 17128064, 18128128, 18128064, 19128128, 29128128):  # 2 pieces: the backward pass of bf16x6b3
-            out.append((case, code, 2))
-        out.append((case, 1128064, 1))
-        for code in (128128, 1064064, 2128064, 3128128, 4128128, 5064064, 6128064, 7064128, 8128128, 8128064, 9128128, 9128064,
-                     10128128, 11128128, 11128064, 12128128, 13128128, 14128128, 15128128,
-                     16128128, 16128064, 17128128, 18128128, 18128064, 19128128, 29128128):  # two fp16 pieces / 3 products (the forward of f16x3b3)
-            out.append((case, code, 22))
+    for case in cases:
+        for pieces, codes in lists.items():
+            for code in codes:
+                out.append((case, code, pieces))
     return out
 
 
-@pytest.mark.parametrize("case,code,pieces", _split_cases())
+_REF64 = {}  # (test, case) -> torch fp64 reference of that geometry, computed once per module
+
+
+def _gather_ref(case):
+    """(x, w, b, dy, y, dx) in fp64 on the host for the split gather tests (one draw per geometry)."""
+    if ("gather", case) not in _REF64:
+        B, L, Cin, Cout, k, s, p, tr = case
+        g = torch.Generator().manual_seed(11 + sum(case[:7]))
+        x = torch.randn(B, Cin, L, generator=g, dtype=torch.float64, requires_grad=True)
+        w = torch.randn(*((Cin, Cout, k) if tr else (Cout, Cin, k)), generator=g, dtype=torch.float64) / math.sqrt(Cin * k)
+        b = torch.randn(Cout, generator=g, dtype=torch.float64)
+        y = (F.conv_transpose1d if tr else F.conv1d)(x, w, b, stride=s, padding=p)
+        dy = torch.randn(y.shape, generator=g, dtype=torch.float64)
+        y.backward(dy)
+        _REF64[("gather", case)] = (x.detach(), w, b, dy, y.detach(), x.grad)
+    return _REF64[("gather", case)]
+
+
+# existing test ids keep their index: the added pairs and the mid-size geometries come after the original list
+@pytest.mark.parametrize("case,code,pieces", _split_cases(CONV_CASES) + _split_cases(CONV_CASES, _SPLIT_GATHER_TABLE)
+                         + _split_cases(MID_CASES) + _split_cases(MID_CASES, _SPLIT_GATHER_TABLE))
 def test_split_gather_kernels(ops, case, code, pieces):
     """Forward / data-gradient on the bf16 matrix cores with 3 / 2 / 1 bf16 pieces per operand
-    (csrc/gemm_bf16s.hip) against torch fp64; 3 pieces must meet the fp32 kernels' tolerance."""
+    (csrc/gemm_bf16s.hip) against torch fp64; 3 pieces must meet the fp32 kernels' tolerance.  The data-gradient's fused
+    activation-backward epilogue runs in its bare-PReLU and BatchNorm + tanh modes (test_gpu_tile_table: BatchNorm + PReLU)."""
     B, L, Cin, Cout, k, s, p, tr = case
-    g = torch.Generator().manual_seed(11 + sum(case[:7]))
-    x = torch.randn(B, Cin, L, generator=g, dtype=torch.float64, requires_grad=True)
-    w = torch.randn(*((Cin, Cout, k) if tr else (Cout, Cin, k)), generator=g, dtype=torch.float64) / math.sqrt(Cin * k)
-    b = torch.randn(Cout, generator=g, dtype=torch.float64)
-    y = (F.conv_transpose1d if tr else F.conv1d)(x, w, b, stride=s, padding=p)
-    dy = torch.randn(y.shape, generator=g, dtype=torch.float64)
-    y.backward(dy)
+    x, w, b, dy, y, x_grad = _gather_ref(case)
     cv = ops.Conv(B, L, Cin, Cout, k, s, p, 1, tr, pieces=pieces)
     if pieces == 22:  # fp16 pieces exist for the forward only: the data-gradient of this mode runs two bf16 pieces
         cv.dgrad_pieces = cv.wgrad_pieces = 2
@@ -642,26 +680,46 @@ def test_split_gather_kernels(ops, case, code, pieces):
     dxd = torch.full((B * L, cv.c_in_p), float("nan"), device="cuda")
     cv.dgrad(to_nlc(dy), wd, dxd)
     tol_d = _SPLIT_TOL[2] if pieces == 22 else tol
-    assert relerr(from_nlc(dxd, B, L, Cin), x.grad) < tol_d * math.sqrt(Cout * k) + tol_d
+    assert relerr(from_nlc(dxd, B, L, Cin), x_grad) < tol_d * math.sqrt(Cout * k) + tol_d
     assert not torch.isnan(dxd).any()
+    assert cv.dgrad_stats_tiles()[0] > 0
+    dx_ref = torch.zeros(B * L, cv.c_in_p, dtype=torch.float64)
+    dx_ref[:, :Cin] = x_grad.permute(0, 2, 1).reshape(B * L, Cin)
+    dx_ref = dx_ref.cuda()
+    for mode in ("bare", "bn_tanh"):
+        acc, *_ = bn_bwd_fused_check(ops, cv, to_nlc(dy), wd, dx_ref, tol_d * math.sqrt(Cout * k) + tol_d, mode, seed=len(mode))
+        bn_bwd_fused_check(ops, cv, to_nlc(dy), wd, dx_ref, tol_d * math.sqrt(Cout * k) + tol_d, mode, accumulate_onto=acc,
+                           seed=len(mode))
 
 
-@pytest.mark.parametrize("case", CONV_CASES)
+def _wgrad_ref(case):
+    """(x, dy, l_out, dw) in fp64 on the host for the split weight-gradient tests (one draw per geometry)."""
+    if ("wgrad", case) not in _REF64:
+        B, L, Cin, Cout, k, s, p, tr = case
+        g = torch.Generator().manual_seed(13 + sum(case[:7]))
+        x = torch.randn(B, Cin, L, generator=g, dtype=torch.float64)
+        w = (torch.randn(*((Cin, Cout, k) if tr else (Cout, Cin, k)), generator=g, dtype=torch.float64)).requires_grad_(True)
+        y = (F.conv_transpose1d if tr else F.conv1d)(x, w, None, stride=s, padding=p)
+        dy = torch.randn(y.shape, generator=g, dtype=torch.float64)
+        y.backward(dy)
+        _REF64[("wgrad", case)] = (x, dy, y.shape[-1], w.grad)
+    return _REF64[("wgrad", case)]
+
+
+@pytest.mark.parametrize("case", CONV_CASES + MID_CASES)
 @pytest.mark.parametrize("code,pieces", [(128128, 3), (64128, 3), (128064, 3), (64064, 3), (0, 3), (64064, 2), (128064, 1),
                                          (256256, 2), (1256256, 2), (256128, 2), (1128256, 2), (1256256, 3), (1256128, 3),
                                          (1128128, 3), (1064128, 3), (1128064, 3), (1064064, 3),
                                          (2256256, 2), (3256128, 2), (2128128, 2), (3064064, 2), (2064128, 3),
                                          (4064128, 2), (6064128, 2), (4128064, 2), (6128064, 2), (4128128, 2), (6128128, 2),
                                          (12064128, 2), (14128064, 2), (12128128, 2), (14128128, 2),
-                                         (16064128, 2), (18128128, 2), (17064064, 3), (16128064, 2), (18128064, 2)])
+                                         (16064128, 2), (18128128, 2), (17064064, 3), (16128064, 2), (18128064, 2),
+                                         # 2-piece codes the shipped tile table selects that the list above did not force
+                                         (14064128, 2), (1128128, 2), (2128064, 2), (17064128, 2), (18064128, 2), (128128, 2),
+                                         (1128064, 2), (12128064, 2), (3128128, 2), (3256256, 2)])
 def test_split_wgrad_kernels(ops, case, code, pieces):
     B, L, Cin, Cout, k, s, p, tr = case
-    g = torch.Generator().manual_seed(13 + sum(case[:7]))
-    x = torch.randn(B, Cin, L, generator=g, dtype=torch.float64)
-    w = (torch.randn(*((Cin, Cout, k) if tr else (Cout, Cin, k)), generator=g, dtype=torch.float64)).requires_grad_(True)
-    y = (F.conv_transpose1d if tr else F.conv1d)(x, w, None, stride=s, padding=p)
-    dy = torch.randn(y.shape, generator=g, dtype=torch.float64)
-    y.backward(dy)
+    x, dy, l_out, w_grad = _wgrad_ref(case)
     cv = ops.Conv(B, L, Cin, Cout, k, s, p, 1, tr, pieces=pieces)
     cv.__dict__["_tuned"] = {"fwd", "dgrad", "wgrad"}
     cv.desc.tile[2] = code
@@ -677,11 +735,11 @@ def test_split_wgrad_kernels(ops, case, code, pieces):
             pytest.skip("geometry outside the all-taps kernel (odd-length strided transposed conv, > 6 taps): the tuner skips it the same way")
         raise
     tol = _SPLIT_TOL[pieces]
-    bound = tol * math.sqrt(B * y.shape[-1]) + tol
-    assert relerr(ops.conv_weight_from_tio(dwd.cpu(), Cin, Cout, tr), w.grad) < bound
+    bound = tol * math.sqrt(B * l_out) + tol
+    assert relerr(ops.conv_weight_from_tio(dwd.cpu(), Cin, Cout, tr), w_grad) < bound
     assert not torch.isnan(dwd).any()
     cv.wgrad(xd, dyd, dwd, dbd, ws, accumulate=True)
-    assert relerr(ops.conv_weight_from_tio(dwd.cpu(), Cin, Cout, tr), 2 * w.grad) < bound
+    assert relerr(ops.conv_weight_from_tio(dwd.cpu(), Cin, Cout, tr), 2 * w_grad) < bound
 
 
 @pytest.mark.parametrize("geo", [(3, 4, 48, 40), (5, 7, 32, 64), (2, 25, 16, 32), (64, 13, 128, 64), (300, 4, 64, 128)])
