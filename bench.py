@@ -9,20 +9,22 @@
 Headline workload = BASELINE.json configs[2] (the N=1 point of the configs[3] data-parallel series): the FULL SC-VAE --
 conditional decoder + two gradient-reversal ensembles + the adversarial net -- on synthetic 64-frame, 23-joint mouse
 skeletons, default residual-CNN channels [64,128,256,512,1024], z=32, 4096 windows per GPU, AdamW.  configs[1] (1024
-windows per GPU, recon + KL only) is measured in the same run at N=1 and reported as the `secondary` object of the same
-JSON line (`--workload config1` makes it the headline instead).
+windows per GPU, recon + KL only) is measured in the same --full run at N=1 and reported as the `secondary` object of the
+same JSON line (`--workload config1` makes it the headline instead).
 
 A step = forward + all configured losses + backward + grad-norm / clip + optimizer step, inputs already resident in HBM.
 Arithmetic: fp32 storage and accumulation everywhere; the large contractions run on the matrix cores with every fp32 operand
 split into 16-bit pieces (default `--precision f16x3b3`: forward = two FP16 pieces per operand, i.e. 22 of its 24 significand
-bits, and their 3 cross products -- outputs, losses and the ELBO match the fp32 CPU oracle to ~1e-7, checked in every run by
-`elbo_match` --; data- and weight-gradient contractions = two BF16 pieces / 3 products; `--precision bf16x6b3` runs the forward
-with three bf16 pieces / 6 products instead).
+bits, and their 3 cross products -- outputs, losses and the ELBO match the fp32 CPU oracle to ~1e-7, checked in every --full
+run by `elbo_match` --; data- and weight-gradient contractions = two BF16 pieces / 3 products; `--precision bf16x6b3` runs the
+forward with three bf16 pieces / 6 products instead).
 Weak scaling: the per-GPU batch is fixed as N grows; every loss is normalised by the global batch and gradients are summed
 over ranks with RCCL.  BatchNorm batch statistics are per rank by default (the semantics of torch DistributedDataParallel
 around the reference model); `--sync-bn` all-reduces them so that N ranks reproduce the 1-rank step at the global batch.
 
-Prints ONE JSON line (rank 0) with the contract fields plus
+Prints ONE JSON line (rank 0) with the contract fields.  A plain run does only what they need: it sets up, warms up, times
+the K steps, writes --dump-outputs if asked and prints the line.  `--full` adds, after the timed steps (which it leaves as
+they are):
   roofline     -- the dominant GEMM kernel template: algorithmic FLOPs per launch over its mean launch time, measured live
                   with HIP events in a second timed region (side streams serialised), against the dense bf16 MFMA peak
                   divided by the matrix-core products per algorithmic multiply; `traffic` = HBM bytes per launch from the
@@ -32,6 +34,7 @@ Prints ONE JSON line (rank 0) with the contract fields plus
                   first step is also the reference of the metric's ELBO-match condition (`elbo_match`: the HIP path with
                   the oracle's weights, batch, noise and shuffle, every loss term within 1e-4 relative);
   secondary    -- configs[1] measured the same way (N=1 only).
+(`--no-roofline`, `--no-cpu-baseline`, `--no-secondary` leave one of them out of a --full run.)
 `--dump-outputs DIR` (e.g. bench_outputs/, which git ignores) also writes what the headline workload's last timed step
 computed as DIR/<name>.npy (dump_outputs): the inputs are seeded, so two builds run with the same arguments can be compared
 output for output.
@@ -66,7 +69,10 @@ def parse():
                     help="headline workload: config2 = BASELINE configs[2], full SC-VAE heads, 4096 windows/GPU (default); "
                          "config1 = configs[1], recon+KL, 1024 windows/GPU")
     ap.add_argument("--batch", type=int, default=None, help="windows per GPU (default: the workload's)")
-    ap.add_argument("--full", action="store_true", help="force the full head set (conditional + grad-reversal + adversarial) on")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the roofline region, the CPU oracle baseline with its ELBO-match check "
+                         "and configs[1] as `secondary` (a plain run measures the headline workload only)")
+    ap.add_argument("--heads", action="store_true", help="force the full head set (conditional + grad-reversal + adversarial) on")
     ap.add_argument("--no-heads", action="store_true", help="force recon + KL only")
     ap.add_argument("--joints", type=int, default=23)
     ap.add_argument("--window", type=int, default=64)
@@ -88,9 +94,9 @@ def parse():
     ap.add_argument("--h2d", action="store_true",
                     help="copy the batch from pinned host memory inside every timed step (the PCIe-inclusive rate DESIGN.md quotes; "
                          "never the headline value: the metric is defined with inputs resident in HBM)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the configs[1] measurement reported as `secondary`")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU oracle baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the roofline region")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the configs[1] measurement reported as `secondary`")
     ap.add_argument("--timer-kinds", default="fwd,dgrad,wgrad", help="GEMM kinds bracketed with HIP events (fwd,dgrad,wgrad)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the headline workload's last timed step computed (loss terms, model "
@@ -102,7 +108,7 @@ def parse():
     wl = WORKLOADS[args.workload]
     if args.batch is None:
         args.batch = wl["batch"]
-    args.full = (wl["full"] or args.full) and not args.no_heads
+    args.heads = (wl["full"] or args.heads) and not args.no_heads
     return args
 
 
@@ -518,7 +524,8 @@ def main():
         ones = torch.ones(1, device="cuda" if backend == "nccl" else "cpu")
         torch.distributed.all_reduce(ones)  # every rank contributes 1: the number of ranks the collective really spans
         ranks_seen = int(ones.item())
-    head = run_workload(args, args.full, B, rank, world, roofline=not args.no_roofline, dump=args.dump_outputs if rank == 0 else None)
+    head = run_workload(args, args.heads, B, rank, world, roofline=args.full and not args.no_roofline,
+                        dump=args.dump_outputs if rank == 0 else None)
 
     if rank == 0:
         out = {
@@ -552,13 +559,14 @@ def main():
         # last parallel region, and the batch-1024 workload -- whose host enqueue time is close to its GPU time -- measured 25 %
         # slower right behind them
         sec = None
-        if world == 1 and not args.no_secondary and args.workload == "config2" and args.batch == WORKLOADS["config2"]["batch"] \
-                and args.channel_list == CHANNELS and args.window == 64 and not (args.graph or args.h2d or args.serial_streams):
+        if world == 1 and args.full and not args.no_secondary and args.workload == "config2" \
+                and args.batch == WORKLOADS["config2"]["batch"] and args.channel_list == CHANNELS and args.window == 64 \
+                and not (args.graph or args.h2d or args.serial_streams):
             w1 = WORKLOADS["config1"]
             sec = run_workload(args, w1["full"], w1["batch"], rank, world, roofline=not args.no_roofline)
             sec = {"metric": out["metric"], "unit": "windows/s", **sec}
-        if not args.no_cpu_baseline and world == 1:  # reported at N=1 only
-            out["cpu_baseline"] = cpu_baseline(args, args.full, B)
+        if args.full and not args.no_cpu_baseline and world == 1:  # reported at N=1 only
+            out["cpu_baseline"] = cpu_baseline(args, args.heads, B)
         if sec is not None:
             if not args.no_cpu_baseline:
                 sec["cpu_baseline"] = cpu_baseline(args, w1["full"], w1["batch"], max_seconds=8.0)

@@ -3,12 +3,14 @@ import json
 import os
 import subprocess
 import sys
+import time
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REQUIRED = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
-            "dtype", "data", "config", "roofline", "cpu_baseline"}
+PLAIN = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+         "dtype", "data", "config"}
+REQUIRED = PLAIN | {"roofline", "cpu_baseline"}      # a --full run
 
 
 def test_bench_defaults_match_baseline_config():
@@ -21,13 +23,20 @@ def test_bench_defaults_match_baseline_config():
     finally:
         sys.argv = old
     assert (a.gpus, a.batch, a.window, a.joints) == (1, 4096, 64, 23)      # BASELINE configs[2]: full SC-VAE, 4096 windows / GPU
-    assert a.channel_list == [64, 128, 256, 512, 1024] and a.full and not a.h2d and not a.graph and not a.no_secondary
+    assert a.channel_list == [64, 128, 256, 512, 1024] and a.heads and not a.h2d and not a.graph and not a.no_secondary
+    assert not a.full                                                      # a plain run: the headline only
     sys.argv = ["bench.py", "--workload", "config1"]
     try:
         a = bench.parse()
     finally:
         sys.argv = old
-    assert (a.batch, a.full) == (1024, False)                              # BASELINE configs[1]
+    assert (a.batch, a.heads) == (1024, False)                             # BASELINE configs[1]
+    sys.argv = ["bench.py", "--full"]
+    try:
+        a = bench.parse()
+    finally:
+        sys.argv = old
+    assert a.full and a.heads and a.batch == 4096                          # --full measures more, the same headline workload
     assert a.precision in bench.PRODUCTS
     assert a.dump_outputs is None
 
@@ -62,7 +71,7 @@ def test_dump_outputs_writes_float_arrays_with_a_fixed_sample(tmp_path):
 @pytest.mark.gpu
 def test_bench_prints_exactly_one_json_line_with_the_contract_fields():
     env = dict(os.environ, PYTHONPATH=ROOT)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2", "--batch", "64"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2", "--batch", "64", "--full"],
                        capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -83,6 +92,29 @@ def test_bench_prints_exactly_one_json_line_with_the_contract_fields():
     c = d["config"]
     assert c["ranks_seen"] == 1 and c["backend"] == "none" and c["bn"] == "single rank"
     assert c["side_streams"] == 0 and c["streams"].startswith("one stream")       # 64 x 64 rows: the serial schedule was timed
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_measures_the_headline_only():
+    """A plain run at the headline workload (configs[2], 4096 windows) sets up, warms up, times its steps and prints the contract
+    fields -- no roofline region, CPU baseline or `secondary` workload (those are --full's) -- within 30 s of the whole run's wall
+    time outside its (warm-up + timed) steps."""
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    steps, warmup = 3, 2
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup)],
+                       capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert PLAIN <= set(d), PLAIN - set(d)
+    assert not {"roofline", "cpu_baseline", "secondary"} & set(d), set(d)
+    assert d["steps"] == steps and d["warmup"] == warmup and d["config"]["batch_per_gpu"] == 4096 and "configs[2]" in d["config"]["workload"]
+    assert abs(d["value"] - 4096 / (d["ms_per_step"] * 1e-3)) <= 0.01 * d["value"]
+    outside = wall - (steps + warmup) * d["ms_per_step"] * 1e-3
+    assert outside <= 30.0, outside
 
 
 @pytest.mark.gpu
@@ -177,11 +209,12 @@ def test_bench_plain_command_becomes_a_launcher_without_touching_the_gpu(monkeyp
 
 @pytest.mark.gpu
 def test_bench_plain_command_line_two_ranks():
-    """Exactly what the driver types -- `python bench.py --gpus 2 ...`, no torchrun -- on the one GPU of the test box (two gloo
-    ranks): the bench launches its own ranks and the line records what the collective really spanned."""
+    """`python bench.py --gpus 2 ... --full`, no torchrun, on the one GPU of the test box (two gloo ranks): the bench launches its
+    own ranks, the line records what the collective really spanned, and the roofline region runs across the ranks."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(PYTHONPATH=ROOT, SVAE_DIST_BACKEND="gloo")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", "64", "--steps", "2", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", "64", "--steps", "2", "--warmup", "1",
+                        "--full"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
