@@ -488,6 +488,78 @@ int svae_ce_sum(const float* logits, int ld, const int* labels, int rows, int C,
 int svae_double_softmax_ce_sum(const float* logits, int ld, int rows, float scale, float* part,
                                float* dlogits, void* stream);
 
+/* ------------------------------------------------------ latent decodability (csrc/decode.hip) --- */
+/* Cross-validated decoders of train()'s test metrics (reference: linear_rand_cv, log_class_rand_cv, qda_rand_cv, mlp_rand_cv,
+ * src/scrubvae/eval/metrics.py:231-329; called at src/scrubvae/train/trainer.py:416-506).  All statistics are fp64.
+ * Rows are the downsampled latents sorted by group (fold, then class); perm[i] = source row of sorted row i.  A fold's rows,
+ * or a (fold, class) group's rows, are one contiguous range [lo[g], hi[g]) of the sorted order (lo / hi: device int arrays). */
+#define SVAE_CV_MAX_DIM 128      /* latent width d */
+#define SVAE_CV_MAX_TARGETS 8    /* regression outputs ny */
+#define SVAE_CV_MAX_CLASSES 64
+#define SVAE_CV_MAX_FOLDS 10
+#define SVAE_CV_MAX_GROUPS 640   /* folds * classes */
+/* mean[d + ny] = column means of x [n][ldx] (first d) and y [n][ldy] (first ny, y may be NULL when ny = 0), then
+ * A[i][:] = [x[perm[i]] - mean_x, 1, y[perm[i]] - mean_y, 0...]  (fp64, lda >= d + 1 + ny) */
+int svae_cv_center(const float* x, int ldx, int d, const float* y, int ldy, int ny, const int* perm, int n, double* mean,
+                   double* A, int lda, void* stream);
+/* out[g] = sum_{r in [lo[g], hi[g])} w[g * ldw + r] A[r][0:D] A[r][0:D]^T  ([D][D] blocks with leading dimension ldo, G <= 640 groups,
+ * w NULL = 1, skip[g] != 0 leaves group g untouched, skip may be NULL).  With the layout of svae_cv_center one block holds the
+ * group's count, sum x, sum x x^T, sum x y^T, sum y and sum y y^T about the global mean; with w = the Hessian weights it is the
+ * logistic Hessian X^T D X.  Rows are summed in ascending order: bit-reproducible. */
+int svae_cv_moments(const double* A, int lda, int D, const int* lo, const int* hi, int G, const double* w, long long ldw,
+                    const int* skip, double* out, int ldo, void* stream);
+/* Batched Cholesky of symmetric positive semi-definite M[b] (n <= 128, row-major, ld ldm, batch <= 640; the lower triangle is
+ * read), one workgroup each with the triangle packed in LDS.
+ * A pivot <= rtol * max(diag M[b]) is a zero direction: its column of L is 0, it adds nothing to logdet and its solution
+ * coefficient is 0; rank[b] counts the kept pivots.  For a dropped direction that is an exact null space of M (a constant or
+ * duplicated latent column) the solution gives the same predictions as the minimum-norm least-squares solution.
+ * Outputs (each may be NULL): L[b] (lower, ld ldm, strideM), logdet[b] = sum log l_kk^2 over kept pivots, rank[b], and
+ * X[b] = M[b]^-1 B[b] for B[b] [n][nrhs] (nrhs <= 8, stride strideB; B NULL: no solve). */
+int svae_spd_factor_solve_f64(const double* M, int ldm, long long strideM, int n, int batch, const double* B, int nrhs,
+                              long long strideB, double* L, double* X, double* logdet, int* rank, double rtol, void* stream);
+/* R^2 statistics per (fold f, output o) over the fold's rows: stats[f][o] = {sum (y - yhat)^2, sum yc, sum yc^2, count}, yc = the
+ * centred target column d + 1 + o of A.  Linear: yhat = A[r][0:d] . beta[f][:, o] + c0[f][o] (beta [folds][d][ny]); MLP: pred != NULL,
+ * a device array of folds fp32 output pointers ([rows][ldp], sorted order), compared with yc + ymean[o]. */
+int svae_cv_r2_stats(const double* A, int lda, int d, int ny, const int* lo, const int* hi, int folds, const double* beta,
+                     const double* c0, const float* const* pred, int ldp, const double* ymean, double* stats, void* stream);
+/* QDA on the test rows of every fold: score_c = cst[f][c] - |L[f][c]^-1 (x - mu[f][c])|^2 / 2 (cst = -logdet/2 + log prior,
+ * -inf = class not in the training fold; mu [folds][K][d], L [folds][K][ldl][ldl]); predicted class = first argmax;
+ * correct[f] += rows with prediction == label (int, zeroed by the caller); pred / gap (top-two score gap) per row may be NULL.
+ * max_rows >= the largest fold. */
+int svae_cv_qda_score(const double* A, int lda, int d, int K, const int* lo, const int* hi, int folds, int max_rows,
+                      const double* mu, const double* L, int ldl, const double* cst, const int* label, int* correct, int* pred,
+                      double* gap, void* stream);
+/* Elastic-net one-vs-rest logistic regression by proximal Newton, one problem p per (fold pfold[p], positive class pos[p]):
+ *   min_w  C sum_{r: fold[r] != pfold[p]} log(1 + exp(-s_r w . A[r][0:D]))  + alpha/2 |w_pen|^2 + rho |w_pen|_1,
+ * s_r = +1 when label[r] == pos[p], D = d + 1 (the last coordinate multiplies A's column of ones: the unpenalised intercept).
+ * One iteration = svae_logreg_stats (loss, gradient partials part[P][chunks][D + 1], Hessian weights hw[P][n]) ->
+ * svae_cv_moments(w = hw) (H) -> svae_logreg_newton (KKT residual; done[p] = 1 below tol * max|grad at w = 0|; else coordinate
+ * descent on the LDS-resident H for the direction) -> svae_logreg_line_search (Armijo over t = 2^-k, k < 12, then w += t dir).
+ * Problems with done[p] != 0 are skipped by every kernel.  kkt_only = 1 only records the residual.  g0 must start at -1, W at 0,
+ * done and iters at 0.  chunks = svae_logreg_chunks(n); the line search needs part of P * chunks * 12 doubles. */
+int svae_logreg_chunks(int n);
+int svae_logreg_stats(const double* A, int lda, int D, int n, const int* fold, const int* label, const int* pfold, const int* pos,
+                      int P, const double* W, double C, const int* done, double* part, double* hw, void* stream);
+int svae_logreg_newton(const double* A, int lda, int D, int n, const int* fold, const int* label, const int* pfold, const int* pos,
+                       int P, const double* part, const double* H, double* W, double* dir, double* f0, double* delta, double* kkt,
+                       double* g0, int* done, int* iters, double alpha, double rho, double tol, int kkt_only, int max_sweeps,
+                       void* stream);
+int svae_logreg_line_search(const double* A, int lda, int D, int n, const int* fold, const int* label, const int* pfold,
+                            const int* pos, int P, double* W, const double* dir, const double* f0, const double* delta, int* done,
+                            int* iters, double C, double alpha, double rho, double* part, void* stream);
+/* decision values of the test rows of fold f with its problems p in [pstart[f], pstart[f + 1]) (pstart: folds + 1 ints; a fold's
+ * problems are those of the classes present in its training rows, as sklearn fits them): argmax (first on a tie) -> pos[p]; a fold
+ * with one problem is binary: decision > 0 -> pos[p], else neg[f].  correct[f] += matches with label (zeroed by the caller), pred may
+ * be NULL */
+int svae_logreg_score(const double* A, int lda, int D, int n, const int* fold, const int* label, const int* pfold, const int* pos,
+                      int P, const double* W, const int* pstart, const int* neg, const int* lo, const int* hi, int folds, int max_rows,
+                      int* correct, int* pred, void* stream);
+/* MLP decoders (train_MLP, metrics.py:307-329) on the svae_ens_* kernels, one ensemble member per fold: dpred[m][r][o] =
+ * 2 (outs[m][r][o] - y[r][o]) for rows outside fold mfold[m], 0 inside (MSELoss(reduction="sum") on the training rows only).
+ * outs / dpred: device arrays of n_members pointers to [n][ld] fp32. */
+int svae_cv_mse_grad(const float* const* outs, float* const* dpred, int n_members, const int* mfold, const float* y, int ldy, int ny,
+                     int ld, const int* fold, int n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -167,6 +167,17 @@ SIGNATURES = {
     "svae_ens_bwd_workspace": (SZ, [C.POINTER(EnsDesc)]),
     "svae_ens_bwd": (I, [C.POINTER(EnsDesc), P, I, F, P, P, SZ, I, P]),
     "svae_ens_loss": (I, [I, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(F), C.POINTER(F), I, P, I, P, I, I, I, P, P]),
+    "svae_cv_center": (I, [P, I, I, P, I, I, P, I, P, P, I, P]),
+    "svae_cv_moments": (I, [P, I, I, P, P, I, P, LL, P, P, I, P]),
+    "svae_spd_factor_solve_f64": (I, [P, I, LL, I, I, P, I, LL, P, P, P, P, D, P]),
+    "svae_cv_r2_stats": (I, [P, I, I, I, P, P, I, P, P, P, I, P, P, P]),
+    "svae_cv_qda_score": (I, [P, I, I, I, P, P, I, I, P, P, I, P, P, P, P, P, P]),
+    "svae_logreg_chunks": (I, [I]),
+    "svae_logreg_stats": (I, [P, I, I, I, P, P, P, P, I, P, D, P, P, P, P]),
+    "svae_logreg_newton": (I, [P, I, I, I, P, P, P, P, I, P, P, P, P, P, P, P, P, P, P, D, D, D, I, I, P]),
+    "svae_logreg_line_search": (I, [P, I, I, I, P, P, P, P, I, P, P, P, P, P, P, D, D, D, P, P]),
+    "svae_logreg_score": (I, [P, I, I, I, P, P, P, P, I, P, P, P, P, P, I, I, P, P, P]),
+    "svae_cv_mse_grad": (I, [P, P, I, P, P, I, I, I, P, I, P]),
 }
 
 _lib = None
@@ -198,6 +209,7 @@ def last_error():
     return buf.value.decode()
 
 
+CV_MAX_DIM, CV_MAX_TARGETS, CV_MAX_CLASSES, CV_MAX_FOLDS, CV_MAX_GROUPS = 128, 8, 64, 10, 640  # include/scrubvae_hip.h SVAE_CV_*
 MAX_LOSS_TERMS = 48  # include/scrubvae_hip.h SVAE_MAX_LOSS_TERMS
 ERR_SHAPE, ERR_ALIGN, ERR_WORKSPACE, ERR_LAUNCH, ERR_ARG = -1, -2, -3, -4, -5  # include/scrubvae_hip.h svae_status
 

@@ -1,0 +1,473 @@
+"""Latent decodability metrics of train() (reference: src/scrubvae/eval/metrics.py:231-329): cross-validated decoders of a
+variable from the latents, on the device.
+
+    linear_rand_cv(z, y_true, window=51, folds=5)     R^2 of least squares (sklearn LinearRegression + r2_score)
+    mlp_rand_cv(z, y_true, window=51, folds=5)        R^2 of the 200-step AdamW MLP of train_MLP
+    log_class_rand_cv(z, y_true, window=51, folds=5)  accuracy of elastic-net one-vs-rest logistic regression
+    qda_rand_cv(z, y_true, window=51, folds=5)        accuracy of QuadraticDiscriminantAnalysis()
+
+Each returns a list of `folds` floats in fold order, as the reference's `rand_cv` wrapper does: rows z[0::window], then
+KFold(n_splits=folds, shuffle=True, random_state=100), restated here in numpy (this module does not import sklearn).  After the
+downsample every pass over the rows, every factorisation and every solver iteration runs in csrc/decode.hip (fp64) or, for the
+MLP, on the fp32 GEMM kernels; the results come back to the host once per call (the MLP's first call at a new size above the
+GEMM autotune threshold also times its tiles once).  Class labels are read on the host first
+(the class set and the row order by class are host decisions).
+
+Differences from the reference, by design:
+  - log_class_rand_cv solves each (fold, class) problem to its optimum (KKT residual <= 1e-8 of the gradient at w = 0) with a
+    deterministic proximal Newton method; the reference's `saga` is randomised and stops at max_iter = 300, possibly short of it.
+    A problem that does not converge within the iteration cap raises a ConvergenceWarning.
+  - a latent direction with (numerically) zero variance in a training fold -- a constant or duplicated column -- gets coefficient 0
+    (svae_spd_factor_solve_f64); for least squares this gives the predictions of sklearn's minimum-norm solution, for QDA the
+    direction is left out of the class density (sklearn divides by its zero variance).
+  - log_class_rand_cv fits, per fold, the classes present in that fold's training rows (sklearn's classes_); a class absent
+    there is never predicted in that fold.
+Limits (ValueError): z_dim <= 128, <= 8 regression targets, <= 64 classes, <= 10 folds.
+"""
+from __future__ import annotations
+
+import warnings
+
+import numpy as np
+import torch
+
+from .. import _lib, ops
+from .._lib import check
+
+_RTOL_PIVOT = 1e-12   # svae_spd_factor_solve_f64: pivots <= this x max diagonal are zero directions
+LOGREG_C, LOGREG_L1_RATIO = 1.0, 0.5
+LOGREG_TOL = 1e-8     # KKT residual relative to max |gradient at w = 0|
+LOGREG_MAX_ITER = 60  # proximal Newton iterations
+LOGREG_MAX_SWEEPS = 500
+MLP_STEPS, MLP_LR, MLP_BETAS, MLP_EPS, MLP_WD = 200, 1e-3, (0.9, 0.999), 1e-8, 0.01
+
+
+class ConvergenceWarning(UserWarning):
+    """A logistic regression problem stopped at the iteration cap above its KKT tolerance (sklearn's ConvergenceWarning)."""
+
+
+def kfold_assign(n, folds):
+    """fold index of each of n rows under KFold(n_splits=folds, shuffle=True, random_state=100)."""
+    folds = int(folds)
+    if folds < 2:
+        raise ValueError(f"k-fold cross-validation requires at least 2 folds, got {folds}")
+    if n < folds:
+        raise ValueError(f"Cannot have number of splits n_splits={folds} greater than the number of samples: n_samples={n}.")
+    idx = np.arange(n)
+    np.random.RandomState(100).shuffle(idx)
+    sizes = np.full(folds, n // folds, dtype=np.int64)
+    sizes[: n % folds] += 1
+    fold = np.empty(n, dtype=np.int64)
+    start = 0
+    for f, s in enumerate(sizes):
+        fold[idx[start: start + s]] = f
+        start += s
+    return fold
+
+
+def _device_of(z):
+    if torch.is_tensor(z) and z.is_cuda:
+        return z.device
+    if not torch.cuda.is_available():
+        raise RuntimeError("the decodability metrics run on the GPU (csrc/decode.hip); no device is available")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _rows(z, window, device):
+    """z[0::window] as a contiguous fp32 [n, d] device tensor."""
+    t = z if torch.is_tensor(z) else torch.from_numpy(np.asarray(z))
+    t = t[0::window]
+    if t.dim() != 2:
+        t = t.reshape(t.shape[0], -1)
+    return t.to(device=device, dtype=torch.float32).contiguous()
+
+
+def _host(y, window):
+    a = y.detach().cpu().numpy() if torch.is_tensor(y) else np.asarray(y)
+    return a[0::window]
+
+
+def _check_dims(n, d, folds, ny=0, k=0):
+    if d > _lib.CV_MAX_DIM:
+        raise ValueError(f"z_dim {d} > {_lib.CV_MAX_DIM}")
+    if ny > _lib.CV_MAX_TARGETS:
+        raise ValueError(f"{ny} regression targets > {_lib.CV_MAX_TARGETS}")
+    if k > _lib.CV_MAX_CLASSES:
+        raise ValueError(f"{k} classes > {_lib.CV_MAX_CLASSES}")
+    if folds > _lib.CV_MAX_FOLDS:
+        raise ValueError(f"{folds} folds > {_lib.CV_MAX_FOLDS}")
+
+
+def _i32(a, device):
+    return torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32)).to(device)
+
+
+class _Rows:
+    """Downsampled rows sorted by group (fold-major), their fold segments and the centred fp64 matrix A of csrc/decode.hip."""
+
+    def __init__(self, x, fold, cls, K, y, device):
+        n, d = x.shape
+        self.n, self.d, self.K, self.device = n, d, K, device
+        group = fold * K + cls
+        self.perm = np.argsort(group, kind="stable")
+        self.fold, self.cls = fold[self.perm], cls[self.perm]
+        F = int(fold.max()) + 1
+        self.folds = F
+        gcount = np.bincount(group, minlength=F * K)
+        self.ghi = np.cumsum(gcount)
+        self.glo = self.ghi - gcount
+        self.flo, self.fhi = self.glo[0::K], self.ghi[K - 1::K]
+        self.ny = 0 if y is None else y.shape[1]
+        self.lda = ops.pad16(d + 1 + self.ny)
+        self.perm_d = _i32(self.perm, device)
+        self.mean = torch.empty(d + self.ny, dtype=torch.float64, device=device)
+        self.A = torch.empty(n, self.lda, dtype=torch.float64, device=device)
+        check(_lib.lib().svae_cv_center(x.data_ptr(), d, d, None if y is None else y.data_ptr(), self.ny, self.ny, self.perm_d.data_ptr(),
+                                        n, self.mean.data_ptr(), self.A.data_ptr(), self.lda, ops._stream()), "cv_center")
+        self.fold_d, self.cls_d = _i32(self.fold, device), _i32(self.cls, device)
+        self.flo_d, self.fhi_d = _i32(self.flo, device), _i32(self.fhi, device)
+        self.max_fold = int((self.fhi - self.flo).max())
+
+    def moments(self, D, lo, hi, w=None, ldw=0, skip=None, out=None):
+        G = len(lo) if not torch.is_tensor(lo) else lo.numel()
+        lo_d = lo if torch.is_tensor(lo) else _i32(lo, self.device)
+        hi_d = hi if torch.is_tensor(hi) else _i32(hi, self.device)
+        if out is None:
+            out = torch.empty(G, D, D, dtype=torch.float64, device=self.device)
+        check(_lib.lib().svae_cv_moments(self.A.data_ptr(), self.lda, D, lo_d.data_ptr(), hi_d.data_ptr(), G, ops._p(w), ldw, ops._p(skip),
+                                         out.data_ptr(), D, ops._stream()), "cv_moments")
+        return out
+
+
+def spd_factor_solve(M, B=None, rtol=_RTOL_PIVOT):
+    """Batched rank-revealing Cholesky (csrc/decode.hip) of fp64 device matrices M [b, n, n] (n <= 128): (L, logdet, rank, X) with
+    X = M^-1 B for B [b, n, nrhs] (nrhs <= 8), pivots <= rtol * max diag treated as zero directions (coefficient 0)."""
+    M = M.contiguous()
+    b, n = M.shape[0], M.shape[1]
+    L = torch.empty_like(M)
+    logdet = torch.empty(b, dtype=torch.float64, device=M.device)
+    rank = torch.empty(b, dtype=torch.int32, device=M.device)
+    X, nrhs = None, 0
+    if B is not None:
+        B = B.contiguous()
+        nrhs = B.shape[2]
+        X = torch.empty_like(B)
+    check(_lib.lib().svae_spd_factor_solve_f64(M.data_ptr(), n, n * n, n, b, ops._p(B), nrhs, n * nrhs, L.data_ptr(), ops._p(X),
+                                               logdet.data_ptr(), rank.data_ptr(), rtol, ops._stream()), "spd_factor_solve_f64")
+    return L, logdet, rank, X
+
+
+def _train_blocks(M, F, K=1):
+    """per (fold, class) moment blocks of the training folds: (sum over folds of the class) - (the fold's own block), fp64"""
+    M = M.view(F, K, *M.shape[1:])
+    tot = M[0].clone()
+    for f in range(1, F):
+        tot += M[f]
+    return tot.unsqueeze(0) - M
+
+
+def _r2_from_stats(st):
+    """sklearn r2_score(multioutput="uniform_average", force_finite=True) per fold from stats [F, ny, 4]"""
+    out = []
+    for f in range(st.shape[0]):
+        r2 = []
+        for o in range(st.shape[1]):
+            ss_res, sy, syy, m = st[f, o]
+            ss_tot = max(syy - sy * sy / m, 0.0)
+            if ss_tot <= 1e-13 * max(syy, 1e-300):  # a constant target: the exact zero of sklearn's two-pass sum
+                r2.append(1.0 if ss_res == 0.0 else 0.0)
+            else:
+                r2.append(1.0 - ss_res / ss_tot)
+        out.append(float(np.mean(r2)))
+    return out
+
+
+def _targets(y_true, window, device):
+    y = _host(y_true, window).astype(np.float32)
+    if y.ndim == 1:
+        y = y[:, None]
+    return torch.from_numpy(np.ascontiguousarray(y.reshape(y.shape[0], -1))).to(device)
+
+
+def linear_rand_cv(z, y_true, window=51, folds=5):
+    """R^2 per fold of least squares with intercept (reference metrics.py:264-269)."""
+    dev = _device_of(z)
+    with torch.cuda.device(dev):
+        x = _rows(z, window, dev)
+        y = _targets(y_true, window, dev)
+        n, d = x.shape
+        ny = y.shape[1]
+        _check_dims(n, d, folds, ny=ny)
+        fold = kfold_assign(n, folds)
+        R = _Rows(x, fold, np.zeros(n, dtype=np.int64), 1, y, dev)
+        D = d + 1 + ny
+        T = _train_blocks(R.moments(D, R.flo, R.fhi), R.folds)[:, 0]
+        cnt = T[:, d, d]
+        sx, sy = T[:, :d, d], T[:, d, d + 1:]
+        cxx = T[:, :d, :d] - sx[:, :, None] * sx[:, None, :] / cnt[:, None, None]
+        cxy = T[:, :d, d + 1:] - sx[:, :, None] * sy[:, None, :] / cnt[:, None, None]
+        _, _, _, beta = spd_factor_solve(cxx, cxy)
+        xbar, ybar = sx / cnt[:, None], sy / cnt[:, None]
+        c0 = (ybar - torch.einsum("fi,fio->fo", xbar, beta)).contiguous()
+        stats = torch.empty(R.folds, ny, 4, dtype=torch.float64, device=dev)
+        check(_lib.lib().svae_cv_r2_stats(R.A.data_ptr(), R.lda, d, ny, R.flo_d.data_ptr(), R.fhi_d.data_ptr(), R.folds, beta.data_ptr(),
+                                          c0.data_ptr(), None, 0, None, stats.data_ptr(), ops._stream()), "cv_r2_stats")
+        return _r2_from_stats(stats.cpu().numpy())
+
+
+def _labels(y_true, window):
+    y = _host(y_true, window).reshape(-1)
+    classes, cls = np.unique(y, return_inverse=True)
+    return classes, cls.astype(np.int64)
+
+
+def _qda(z, y_true, window, folds, want_rows=False):
+    dev = _device_of(z)
+    with torch.cuda.device(dev):
+        x = _rows(z, window, dev)
+        n, d = x.shape
+        classes, cls = _labels(y_true, window)
+        K = len(classes)
+        _check_dims(n, d, folds, k=K)
+        if K < 2:
+            raise ValueError(f"The number of classes has to be greater than one; got {K} class")
+        fold = kfold_assign(n, folds)
+        R = _Rows(x, fold, cls, K, None, dev)
+        F = R.folds
+        cnt_fc = (R.ghi - R.glo).reshape(F, K)
+        train_cnt = cnt_fc.sum(0)[None, :] - cnt_fc
+        if (train_cnt == 1).any():
+            f, c = np.argwhere(train_cnt == 1)[0]
+            raise ValueError(f"y has only 1 sample in class {classes[c]} (training set of fold {f}), covariance is ill defined.")
+        if ((train_cnt > 0).sum(1) < 2).any():
+            raise ValueError("a training fold holds fewer than two classes")
+        D = d + 1
+        T = _train_blocks(R.moments(D, R.glo, R.ghi), F, K).reshape(F * K, D, D)
+        cnt = T[:, d, d].clamp(min=2.0)
+        sx = T[:, :d, d]
+        mu = (sx / cnt[:, None]).contiguous()
+        cov = (T[:, :d, :d] - sx[:, :, None] * sx[:, None, :] / cnt[:, None, None]) / (cnt - 1.0)[:, None, None]
+        absent = torch.as_tensor((train_cnt == 0).reshape(-1), device=dev)
+        cov[absent] = torch.eye(d, dtype=torch.float64, device=dev)
+        L, logdet, _, _ = spd_factor_solve(cov)
+        with np.errstate(divide="ignore"):
+            logprior = np.log(train_cnt / train_cnt.sum(1, keepdims=True)).reshape(-1)
+        cst = (torch.as_tensor(logprior, device=dev) - 0.5 * logdet).contiguous()
+        correct = torch.zeros(F, dtype=torch.int32, device=dev)
+        pred = torch.empty(n, dtype=torch.int32, device=dev) if want_rows else None
+        gap = torch.empty(n, dtype=torch.float64, device=dev) if want_rows else None
+        check(_lib.lib().svae_cv_qda_score(R.A.data_ptr(), R.lda, d, K, R.flo_d.data_ptr(), R.fhi_d.data_ptr(), F, R.max_fold,
+                                           mu.data_ptr(), L.data_ptr(), d, cst.data_ptr(), R.cls_d.data_ptr(), correct.data_ptr(),
+                                           ops._p(pred), ops._p(gap), ops._stream()), "cv_qda_score")
+        acc = [float(c) / float(m) for c, m in zip(correct.cpu().numpy(), R.fhi - R.flo)]
+        if not want_rows:
+            return acc
+        out = dict(acc=acc, perm=R.perm, fold=R.fold, pred=np.empty(n, np.int64), gap=np.empty(n))
+        out["pred"][R.perm] = classes[pred.cpu().numpy()]
+        out["gap"][R.perm] = gap.cpu().numpy()
+        return out
+
+
+def qda_rand_cv(z, y_true, window=51, folds=5):
+    """Accuracy per fold of QuadraticDiscriminantAnalysis() (reference metrics.py:287-292)."""
+    return _qda(z, y_true, window, folds)
+
+
+def logreg_problems(cnt_fc):
+    """The one-vs-rest problems sklearn fits on each training fold, from the per-(fold, class) row counts [F, K]: the classes
+    present in the fold's training rows; two present classes make one binary problem with the second one positive.  Returns
+    (pfold [P], pos [P] class index, pstart [F + 1], neg [F]: the negative class of a binary fold, else -1)."""
+    F, K = cnt_fc.shape
+    train = cnt_fc.sum(0)[None, :] - cnt_fc
+    pfold, pos, pstart, neg = [], [], [0], []
+    for f in range(F):
+        present = np.nonzero(train[f] > 0)[0]
+        if len(present) < 2:
+            raise ValueError(f"This solver needs samples of at least 2 classes in the data, but the training rows of fold {f} "
+                             f"contain {len(present)} class(es)")
+        use = present[1:] if len(present) == 2 else present
+        pfold += [f] * len(use)
+        pos += list(use)
+        pstart.append(len(pos))
+        neg.append(int(present[0]) if len(present) == 2 else -1)
+    return np.array(pfold), np.array(pos), np.array(pstart), np.array(neg)
+
+
+def _logreg(z, y_true, window, folds, want_rows=False):
+    dev = _device_of(z)
+    with torch.cuda.device(dev):
+        x = _rows(z, window, dev)
+        n, d = x.shape
+        classes, cls = _labels(y_true, window)
+        K = len(classes)
+        _check_dims(n, d, folds, k=K)
+        if K < 2:
+            raise ValueError(f"This solver needs samples of at least 2 classes in the data, but the data contains only one class: {classes}")
+        fold = kfold_assign(n, folds)
+        R = _Rows(x, fold, cls, K, None, dev)
+        F = R.folds
+        pf, ps, pstart_h, neg_h = logreg_problems((R.ghi - R.glo).reshape(F, K))
+        P = len(pf)
+        pfold, pos = _i32(pf, dev), _i32(ps, dev)
+        pstart, neg = _i32(pstart_h, dev), _i32(neg_h, dev)
+        D = d + 1
+        L = _lib.lib()
+        st = ops._stream()
+        chunks = L.svae_logreg_chunks(n)
+        f64 = dict(dtype=torch.float64, device=dev)
+        W = torch.zeros(P, D, **f64)
+        dirn = torch.zeros(P, D, **f64)
+        f0, delta, kkt = (torch.zeros(P, **f64) for _ in range(3))
+        g0 = torch.full((P,), -1.0, **f64)
+        done = torch.zeros(P, dtype=torch.int32, device=dev)
+        iters = torch.zeros(P, dtype=torch.int32, device=dev)
+        part = torch.empty(P * chunks * max(D + 1, 12), **f64)
+        hw = torch.empty(P, n, **f64)
+        H = torch.empty(P, D, D, **f64)
+        lo_all, hi_all = _i32(np.zeros(P), dev), _i32(np.full(P, n), dev)
+        C, rho = LOGREG_C, LOGREG_L1_RATIO
+        alpha = 1.0 - rho
+        prob = (R.A.data_ptr(), R.lda, D, n, R.fold_d.data_ptr(), R.cls_d.data_ptr(), pfold.data_ptr(), pos.data_ptr(), P)
+        state = (W.data_ptr(), dirn.data_ptr(), f0.data_ptr(), delta.data_ptr(), kkt.data_ptr(), g0.data_ptr(), done.data_ptr(),
+                 iters.data_ptr())
+        for it in range(LOGREG_MAX_ITER + 1):
+            last = it == LOGREG_MAX_ITER
+            check(L.svae_logreg_stats(*prob, W.data_ptr(), C, done.data_ptr(), part.data_ptr(), hw.data_ptr(), st), "logreg_stats")
+            if not last:
+                R.moments(D, lo_all, hi_all, w=hw, ldw=n, skip=done, out=H)
+            check(L.svae_logreg_newton(*prob, part.data_ptr(), H.data_ptr(), *state, alpha, rho, LOGREG_TOL, int(last), LOGREG_MAX_SWEEPS,
+                                       st), "logreg_newton")
+            if last:
+                break
+            check(L.svae_logreg_line_search(*prob, W.data_ptr(), dirn.data_ptr(), f0.data_ptr(), delta.data_ptr(), done.data_ptr(),
+                                            iters.data_ptr(), C, alpha, rho, part.data_ptr(), st), "logreg_line_search")
+        correct = torch.zeros(F, dtype=torch.int32, device=dev)
+        pred = torch.empty(n, dtype=torch.int32, device=dev) if want_rows else None
+        check(L.svae_logreg_score(*prob, W.data_ptr(), pstart.data_ptr(), neg.data_ptr(), R.flo_d.data_ptr(), R.fhi_d.data_ptr(), F, R.max_fold, correct.data_ptr(),
+                                  ops._p(pred), st), "logreg_score")
+        res = torch.cat([correct.double(), kkt, g0]).cpu().numpy()
+        correct_h, kkt_h, g0_h = res[:F], res[F:F + P], res[F + P:]
+        bad = np.nonzero(kkt_h > LOGREG_TOL * g0_h)[0]
+        if len(bad):
+            warnings.warn(f"log_class_rand_cv: {len(bad)} of {P} logistic problems stopped at {LOGREG_MAX_ITER} iterations with a KKT "
+                          f"residual up to {float((kkt_h[bad] / np.maximum(g0_h[bad], 1e-300)).max()):.2e} of the initial gradient",
+                          ConvergenceWarning)
+        acc = [float(c) / float(m) for c, m in zip(correct_h, R.fhi - R.flo)]
+        if not want_rows:
+            return acc
+        Wh = W.cpu().numpy()
+        mean = R.mean.cpu().numpy()
+        coef = Wh[:, :d]
+        intercept = Wh[:, d] - Wh[:, :d] @ mean  # back to raw (uncentred) latents
+        out = dict(acc=acc, coef=coef, intercept=intercept, pfold=pf, pos=classes[ps], pstart=pstart_h, kkt=kkt_h, g0=g0_h,
+                   iters=iters.cpu().numpy(), classes=classes, fold=fold, pred=np.empty(n, np.int64))
+        out["pred"][R.perm] = classes[pred.cpu().numpy()]
+        return out
+
+
+def log_class_rand_cv(z, y_true, window=51, folds=5):
+    """Accuracy per fold of LogisticRegression(penalty="elasticnet", l1_ratio=0.5, multi_class="ovr", C=1) at its optimum
+    (reference metrics.py:272-284)."""
+    return _logreg(z, y_true, window, folds)
+
+
+_MLP_CONVS = {}
+
+
+def _linear_conv(device, rows, c_in, c_out):
+    """fp32 Linear geometry of the MLP decoder, one per (device, rows, c_in, c_out) for the process: a size above the autotune
+    threshold times its tiles on its first call only, later calls reuse the choice (the fp32 kernels' results do not depend on the
+    tile: include/scrubvae_hip.h, svae_conv_desc.tile)."""
+    key = (device.index, rows, c_in, c_out)
+    cv = _MLP_CONVS.get(key)
+    if cv is None:
+        cv = _MLP_CONVS[key] = ops.Conv(rows, 1, c_in, c_out, 1, pieces=0)
+    return cv
+
+
+def mlp_init(d, ny):
+    """Initial weights of the reference's MLP(d, ny) (model/disentangle.py:568-580): three nn.Linear drawn in order from torch's
+    global generator -> list of (weight [out, in], bias [out])."""
+    lins = [torch.nn.Linear(d, d), torch.nn.Linear(d, d), torch.nn.Linear(d, ny)]
+    return [(l.weight.detach().clone(), l.bias.detach().clone()) for l in lins]
+
+
+def mlp_rand_cv(z, y_true, window=51, folds=5, init=None):
+    """R^2 per fold of train_MLP (reference metrics.py:295-329): MLP(d, ny) = Linear-ReLU-Linear-ReLU-Linear, AdamW(lr 1e-3,
+    weight_decay 0.01), 200 full-batch steps on MSELoss(reduction="sum") over the training rows, fp32 on the GEMM kernels.
+    The initial weights are drawn fold by fold as the reference does (mlp_init); `init` (a list of `folds` mlp_init results)
+    overrides them."""
+    dev = _device_of(z)
+    with torch.cuda.device(dev):
+        x = _rows(z, window, dev)
+        y = _targets(y_true, window, dev)
+        n, d = x.shape
+        ny = y.shape[1]
+        _check_dims(n, d, folds, ny=ny)
+        fold = kfold_assign(n, folds)
+        if init is None:
+            init = [mlp_init(d, ny) for _ in range(folds)]
+        R = _Rows(x, fold, np.zeros(n, dtype=np.int64), 1, y, dev)
+        F = R.folds
+        dp, op = ops.pad16(d), ops.pad16(ny)
+        xs = torch.zeros(n, dp, device=dev)
+        xs[:, :d] = x[torch.as_tensor(R.perm, device=dev)]
+        ys = y[torch.as_tensor(R.perm, device=dev)].contiguous()
+        dims = [(d, d), (d, d), (d, ny)]
+        convs = [_linear_conv(dev, n, i, o) for i, o in dims]
+        sizes = [(cv.c_in_p * cv.c_out_p, cv.c_out_p) for cv in convs]
+        total = sum(a + b for a, b in sizes)
+        pre = [torch.zeros(n, cv.c_out_p, device=dev) for cv in convs]
+        act = [torch.zeros(n, dp, device=dev) for _ in range(2)]
+        gbuf = [torch.zeros(n, dp, device=dev) for _ in range(2)]
+        dout = torch.zeros(n, op, device=dev)
+        ws = torch.empty(max(cv.wgrad_workspace_bytes() for cv in convs) // 4 + 64, device=dev)
+        outs = []
+        mfold = torch.zeros(1, dtype=torch.int32, device=dev)
+        ptrs = torch.tensor([pre[2].data_ptr(), dout.data_ptr()], dtype=torch.int64, device=dev)
+        for f in range(F):
+            p = torch.zeros(total, device=dev)
+            g, m, v = torch.zeros_like(p), torch.zeros_like(p), torch.zeros_like(p)
+            views, gviews, off = [], [], 0
+            for (nw, nb), cv, (wt, bt) in zip(sizes, convs, init[f]):
+                w_, b_ = p[off: off + nw].view(1, cv.c_in_p, cv.c_out_p), p[off + nw: off + nw + nb]
+                gw, gb = g[off: off + nw].view(1, cv.c_in_p, cv.c_out_p), g[off + nw: off + nw + nb]
+                w_[0, : wt.shape[1], : wt.shape[0]] = wt.t().to(dev, torch.float32)
+                b_[: bt.shape[0]] = bt.to(dev, torch.float32)
+                views.append((w_, b_))
+                gviews.append((gw, gb))
+                off += nw + nb
+            hyper = torch.tensor([MLP_LR, 0.0, 0.0, 0.0], device=dev)
+            mfold.fill_(f)
+            for _ in range(MLP_STEPS):
+                h = xs
+                for li in range(3):
+                    convs[li].fwd(h, views[li][0], views[li][1], pre[li])
+                    if li < 2:
+                        ops.relu_fwd(pre[li], act[li])
+                        h = act[li]
+                check(_lib.lib().svae_cv_mse_grad(ptrs[0:1].data_ptr(), ptrs[1:2].data_ptr(), 1, mfold.data_ptr(), ys.data_ptr(), ny, ny,
+                                                  op, R.fold_d.data_ptr(), n, ops._stream()), "cv_mse_grad")
+                gy = dout
+                for li in (2, 1, 0):
+                    xin = xs if li == 0 else act[li - 1]
+                    convs[li].wgrad(xin, gy, gviews[li][0], gviews[li][1], ws)
+                    if li > 0:
+                        convs[li].dgrad(gy, views[li][0], gbuf[li - 1])
+                        ops.relu_bwd(gbuf[li - 1], act[li - 1], gbuf[li - 1])
+                        gy = gbuf[li - 1]
+                ops.adam_advance(hyper, *MLP_BETAS)
+                ops.adam_step_dev(p, g, m, v, hyper, MLP_BETAS[0], MLP_BETAS[1], MLP_EPS, MLP_WD, True)
+            h = xs
+            for li in range(3):
+                convs[li].fwd(h, views[li][0], views[li][1], pre[li])
+                if li < 2:
+                    ops.relu_fwd(pre[li], act[li])
+                    h = act[li]
+            outs.append(pre[2].clone())
+        optr = torch.tensor([o.data_ptr() for o in outs], dtype=torch.int64, device=dev)
+        stats = torch.empty(F, ny, 4, dtype=torch.float64, device=dev)
+        ymean = R.mean[d:].contiguous()
+        check(_lib.lib().svae_cv_r2_stats(R.A.data_ptr(), R.lda, d, ny, R.flo_d.data_ptr(), R.fhi_d.data_ptr(), F, None, None,
+                                          optr.data_ptr(), op, ymean.data_ptr(), stats.data_ptr(), ops._stream()), "cv_r2_stats")
+        return _r2_from_stats(stats.cpu().numpy())

@@ -13,6 +13,7 @@ import math
 import time
 from pathlib import Path
 
+import numpy as np
 import torch
 
 from .. import ops
@@ -346,11 +347,55 @@ def train_epoch(config, model, loader, optimizer, scheduler, device="cuda", epoc
     return train_test_epoch(config, model, loader, device, epoch, optimizer, scheduler, mode="train")
 
 
+def decodability_metrics(config, model, loader, z_test):
+    """trainer.py:416-506: cross-validated decodability of the validation latents (scrubvae_amd.eval.metrics, on the device).
+    dataset "4_mice": r2_{avg_speed_3d,heading}_{lin,mlp}_{mean,std} and acc_ids_{log,qda}_{mean,std}; "parkinsons":
+    acc_{ids,pd_label}_{log,qda}_{mean,std}; nothing with train.minimal_test or any other (or no) dataset.  Means and standard
+    deviations over the folds with ddof 0, as np.mean / np.std.  With several ranks each rank computes them on the latents its
+    own test_epoch returned (its shard of the validation set); the latents are not gathered.  A metric the validation data cannot
+    support (fewer downsampled windows than folds, a class with a single training window for QDA, a fold whose training windows
+    hold one class, more than 64 classes) raises ValueError in scrubvae_amd.eval; here that metric's keys are left out with a
+    warning and training goes on."""
+    import warnings
+
+    from .. import eval as E
+    dataset = config.get("data", {}).get("dataset")
+    if config.get("train", {}).get("minimal_test") or dataset not in ("4_mice", "parkinsons"):
+        return {}
+    out = {}
+
+    def target(key):
+        return loader.dataset[:][key].detach().cpu().numpy()
+
+    def record(prefix, fn, y):
+        try:
+            vals = fn(z=z_test, y_true=y, window=model.window, folds=5)
+        except ValueError as e:
+            warnings.warn("decodability metric {} skipped: {}".format(prefix, e))
+            return
+        out[prefix + "_mean"] = float(np.mean(vals))
+        out[prefix + "_std"] = float(np.std(vals))
+
+    if dataset == "4_mice":
+        for key in ["avg_speed_3d", "heading"]:
+            y = target(key)
+            record("r2_{}_lin".format(key), E.linear_rand_cv, y)
+            record("r2_{}_mlp".format(key), E.mlp_rand_cv, y)
+        keys = ["ids"]
+    else:
+        keys = ["ids", "pd_label"]
+    for key in keys:
+        y = target(key).astype(int)
+        record("acc_{}_log".format(key), E.log_class_rand_cv, y)
+        record("acc_{}_qda".format(key), E.qda_rand_cv, y)
+    return out
+
+
 def train(config, model, loader_dict, run=None):
     """trainer.py:322-516: optimizer / scheduler set-up, beta schedule, per-epoch scrubber re-initialisation, tuned
     forgetting factors in the metrics, weights every 5 epochs, optimizer state every 20, `test_epoch` on
-    loader_dict["val"] from epoch 50 on.  The sklearn decodability / clustering metrics (trainer.py:414-507) are
-    outside the path.  Metrics go to `run.log(metrics, epoch)` when a W&B-like `run` is given and are
+    loader_dict["val"] from epoch 50 on, followed by the decodability metrics of trainer.py:416-506 (decodability_metrics; the
+    clustering metrics the reference leaves commented out are not computed).  Metrics go to `run.log(metrics, epoch)` when a W&B-like `run` is given and are
     always appended as JSON lines to <out_path>/metrics.jsonl (the W&B-free log of SURVEY 8f N3)."""
     import json
     optimizer, scheduler = get_optimizer_and_lr_scheduler(
@@ -385,8 +430,9 @@ def train(config, model, loader_dict, run=None):
                         ck["lr_scheduler"] = scheduler.state_dict()
                     torch.save(ck, "{}/checkpoints/epoch_{}.pth".format(out_path, epoch))
             if epoch >= 50 and loader_dict.get("val") is not None:
-                test_metrics, _ = test_epoch(config, model, loader_dict["val"], model.device, epoch)
+                test_metrics, z_test = test_epoch(config, model, loader_dict["val"], model.device, epoch)
                 metrics.update({"{}_test".format(k): float(v) for k, v in test_metrics.items()})
+                metrics.update(decodability_metrics(config, model, loader_dict["val"], z_test))
         if run is not None:
             run.log(metrics, epoch)
         if out_path:
