@@ -560,6 +560,47 @@ int svae_logreg_score(const double* A, int lda, int D, int n, const int* fold, c
 int svae_cv_mse_grad(const float* const* outs, float* const* dpred, int n_members, const int* mfold, const float* y, int ldy, int ny,
                      int ld, const int* fold, int n, void* stream);
 
+/* ---------------------------------------------------------- Gaussian mixture clustering (csrc/gmm.hip) --- */
+/* sklearn GaussianMixture(init_params="k-means++", n_init=1) of the reference's eval/cluster.py::gmm, fp64.  Rows are A [n][lda]
+ * from svae_cv_center (identity perm, ny = 0: columns [0, d) = x - global mean, column d = 1); means mu [K][d] are in that centred
+ * frame.  d <= SVAE_CV_MAX_DIM, K <= SVAE_GMM_MAX_COMPONENTS.  Every reduction runs in a fixed order: bit-reproducible. */
+#define SVAE_GMM_MAX_COMPONENTS 64
+#define SVAE_GMM_MAX_TRIALS 8  /* k-means++ candidates per round: 2 + int(log K) */
+/* One k-means++ round.  vals NULL (the first round): cand[0] (device, set by the caller) is the first center.  Otherwise cand[t] =
+ * searchsorted(prefix sum of closest, vals[t]) clipped to n - 1 for t < T (vals: device, the host's uniform draws times the
+ * current potential).  Then d2[t][r] = min(closest[r], |A[r] - A[cand[t]]|^2) (no minimum on the first round), potentials
+ * summed in a fixed order, the first smallest wins: pot[0], id[0] = its row, best[0] = its t; closest and tot (the block sums
+ * the next round's prefix sum reads) take its distances.  Buffers: closest [n], tot and part [T][blocks], d2 [T][n],
+ * blocks = svae_gmm_kpp_blocks(n). */
+int svae_gmm_kpp_blocks(int n);
+int svae_gmm_kpp_round(const double* A, int lda, int d, int n, const double* vals, int T, int* cand, double* closest, double* tot,
+                       double* d2, double* part, double* pot, int* id, int* best, void* stream);
+/* E-step.  Weighted log density w_k(r) = cst[k] - |(A[r][0:d] - mu[k]) P_k|^2 / 2 with cst = log weight + log det P - d log(2 pi) / 2;
+ * full (diag = 0): P [K][d][ldp] upper triangular (precisions_cholesky_, ldp = pad8(d), zero below the diagonal and in the pad
+ * columns); diag: P [K][d].  Outputs (NULL: not written): resp [K][n] = exp(w_k - logsumexp_k w_k) (needed for lpn and part),
+ * lpn [n] = logsumexp, part [svae_gmm_estep_blocks(n)] = per-block sums of lpn, label [n] = first argmax_k w_k, gap [n] = top-two
+ * gap of w. */
+int svae_gmm_estep_blocks(int n);
+int svae_gmm_estep_f64(const double* A, int lda, int d, int n, int K, int diag, const double* mu, const double* P, int ldp,
+                       const double* cst, double* resp, double* lpn, double* part, int* label, double* gap, void* stream);
+/* out[0] = (x[0] + ... + x[m - 1]) / div in a fixed order (the lower bound from the E-step's part) */
+int svae_gmm_sum_f64(const double* x, int m, double div, double* out, void* stream);
+/* M-step from resp [K][n], as sklearn's _estimate_gaussian_parameters but two-pass about the new means:
+ *   s1 [K][d + 1] = sum_r resp A (column d: the responsibility total), nk = s1[:, d] + 10 eps, mu = s1[:, :d] / nk, w = nk / sum nk;
+ *   full: cov [K][d][d] = sum_r resp (a - mu)(a - mu)^T / nk + reg I (factor it with svae_spd_factor_solve_f64, rtol = 0, then
+ *         svae_gmm_precision_f64);
+ *   diag: cov [K][d] = sum_r resp (a - mu)^2 / nk + reg, P [K][d] = 1 / sqrt(cov), cst as in the E-step, bad[k] = some cov <= 0.
+ * Rows are summed in svae_gmm_chunks(n, d) chunks, each in ascending order, the chunks in order: part holds
+ * chunks * K * max(d + 1, full ? d * d : d) doubles. */
+int svae_gmm_chunks(int n, int d);
+int svae_gmm_mstep_f64(const double* A, int lda, int d, int n, int K, int diag, const double* resp, double reg, double* part,
+                       double* s1, double* nk, double* w, double* mu, double* cov, double* P, double* cst, int* bad, void* stream);
+/* full covariance: P[k] = L[k]^-T ([d][ldp], ldp = pad8(d)) from the Cholesky factors L [K][d][d] and rank [K] of
+ * svae_spd_factor_solve_f64 (rtol = 0), cst[k] = log w[k] + sum log P_jj - d log(2 pi) / 2; bad[k] = rank[k] < d (the covariance
+ * is not positive definite; P[k] and cst[k] are then not written). */
+int svae_gmm_precision_f64(const double* L, const int* rank, const double* w, int d, int K, int ldp, double* P, double* cst, int* bad,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

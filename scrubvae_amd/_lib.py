@@ -178,6 +178,14 @@ SIGNATURES = {
     "svae_logreg_line_search": (I, [P, I, I, I, P, P, P, P, I, P, P, P, P, P, P, D, D, D, P, P]),
     "svae_logreg_score": (I, [P, I, I, I, P, P, P, P, I, P, P, P, P, P, I, I, P, P, P]),
     "svae_cv_mse_grad": (I, [P, P, I, P, P, I, I, I, P, I, P]),
+    "svae_gmm_kpp_blocks": (I, [I]),
+    "svae_gmm_kpp_round": (I, [P, I, I, I, P, I, P, P, P, P, P, P, P, P, P]),
+    "svae_gmm_estep_blocks": (I, [I]),
+    "svae_gmm_estep_f64": (I, [P, I, I, I, I, I, P, P, I, P, P, P, P, P, P, P]),
+    "svae_gmm_sum_f64": (I, [P, I, D, P, P]),
+    "svae_gmm_chunks": (I, [I, I]),
+    "svae_gmm_mstep_f64": (I, [P, I, I, I, I, I, P, D, P, P, P, P, P, P, P, P, P, P]),
+    "svae_gmm_precision_f64": (I, [P, P, P, I, I, I, P, P, P, P]),
 }
 
 _lib = None
@@ -210,6 +218,7 @@ def last_error():
 
 
 CV_MAX_DIM, CV_MAX_TARGETS, CV_MAX_CLASSES, CV_MAX_FOLDS, CV_MAX_GROUPS = 128, 8, 64, 10, 640  # include/scrubvae_hip.h SVAE_CV_*
+GMM_MAX_COMPONENTS, GMM_MAX_TRIALS = 64, 8  # include/scrubvae_hip.h SVAE_GMM_*
 MAX_LOSS_TERMS = 48  # include/scrubvae_hip.h SVAE_MAX_LOSS_TERMS
 ERR_SHAPE, ERR_ALIGN, ERR_WORKSPACE, ERR_LAUNCH, ERR_ARG = -1, -2, -3, -4, -5  # include/scrubvae_hip.h svae_status
 

@@ -471,3 +471,18 @@ def mlp_rand_cv(z, y_true, window=51, folds=5, init=None):
         check(_lib.lib().svae_cv_r2_stats(R.A.data_ptr(), R.lda, d, ny, R.flo_d.data_ptr(), R.fhi_d.data_ptr(), F, None, None,
                                           optr.data_ptr(), op, ymean.data_ptr(), stats.data_ptr(), ops._stream()), "cv_r2_stats")
         return _r2_from_stats(stats.cpu().numpy())
+
+
+def cluster_entropy(k_preds0, k_preds1, n_components):
+    """Mean per-cluster Shannon entropy (bits) of a reference clustering k_preds0 within each cluster i < n_components of
+    k_preds1 (the inner loop of the reference's epoch_cluster_entropy, metrics.py:133-145): the histogram of k_preds0 over the rows
+    with k_preds1 == i, bins np.arange(k_preds0.max() + 2) - 0.5, normalised by the cluster size; an empty cluster adds 0."""
+    k0, k1 = np.asarray(k_preds0).reshape(-1), np.asarray(k_preds1).reshape(-1)
+    bins = np.arange(k0.max() + 2) - 0.5
+    entropy = 0.0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for i in range(n_components):
+            sel = k1 == i
+            hist = np.histogram(k0[sel], bins=bins)[0] / sel.sum()
+            entropy += np.nan_to_num(hist * np.log2(1 / hist)).sum()
+    return float(entropy / n_components)
