@@ -601,6 +601,38 @@ int svae_gmm_mstep_f64(const double* A, int lda, int d, int n, int K, int diag, 
 int svae_gmm_precision_f64(const double* L, const int* rank, const double* w, int d, int K, int ldp, double* P, double* cst, int* bad,
                            void* stream);
 
+/* ---------------------------------------------------------------------- HDBSCAN clustering (csrc/hdbscan.hip) --- */
+/* sklearn HDBSCAN(metric="euclidean") of the reference's eval/cluster.py::dbscan, fp64.  Rows X [n][ld] (the latents converted to
+ * fp64, not centred).  Squared distance s = ((x0 - y0)^2 + (x1 - y1)^2) + ... in feature order, no FMA; distance = sqrt(s),
+ * correctly rounded.  Mutual reachability w_ij = max(core_i, core_j, d_ij / alpha).  MST edges are ordered by the strict key
+ * (w, min(i, j), max(i, j)), so the tree is unique and every result is bit-reproducible.  Any d >= 1, 2 <= n < 2^31. */
+/* core [n] = sqrt of the k-th smallest s over all n rows (the row itself included at 0), 1 <= k <= n; k = 1 writes zeros */
+int svae_hdb_core(const double* X, int ld, int d, int n, int k, double* core, void* stream);
+/* One Boruvka round.  Rows in ascending order of core distance: X [n][ld], core [n], id [n] (the row's index in the caller's order,
+ * used in the key), comp [n] (component ids 0 .. n_comp - 1, n_comp >= 2).  Per row: bw [n], bp [n] = the minimum-key edge to another
+ * component (bp = (lo << 32) | hi of the ids); per component: cw [n_comp] = the bits of its minimum weight, cp [n_comp] = the
+ * minimum packed pair among its rows at that weight.  Copy cw / cp to the host for svae_hdb_merge. */
+int svae_hdb_boruvka(const double* X, int ld, int d, int n, const double* core, const int* id, const int* comp, double alpha, int n_comp,
+                     double* bw, unsigned long long* bp, unsigned long long* cw, unsigned long long* cp, void* stream);
+/* comp[r] = map[comp[r]] for r < n (the relabelling svae_hdb_merge returns) */
+int svae_hdb_relabel(int* comp, int n, const int* map, void* stream);
+/* HOST memory, no stream.  Adds each component's edge (cw, cp) to lo / hi / w [n - 1] at *n_edges (an edge chosen from both sides
+ * once), merges components: comp [n] (caller's row order) relabelled in place, map [n_comp] = new id of each old component,
+ * *n_comp_out = the new count (ids numbered by first old component). */
+int svae_hdb_merge(int n, int n_comp, const unsigned long long* cw, const unsigned long long* cp, int* comp, int* map, int* lo, int* hi,
+                   double* w, int* n_edges, int* n_comp_out);
+/* HOST memory, no stream.  From the n - 1 MST edges (lo < hi, any order): the single-linkage tree sl_* [n - 1] (edges in key order,
+ * the root of lo on the left, internal node n + edge index), then sklearn 1.7's condensed tree (lambda = 1 / w, inf at w = 0),
+ * stabilities, excess-of-mass (leaf = 0) or leaf (leaf = 1) selection with epsilon, max_cluster_size (<= 0: none) and
+ * allow_single_cluster, labels [n] (-1 noise, clusters numbered in ascending condensed node order) and prob [n]. */
+int svae_hdb_tree(int n, const int* lo, const int* hi, const double* w, int min_cluster_size, int leaf, int allow_single, double epsilon,
+                  long long max_cluster_size, long long* sl_left, long long* sl_right, double* sl_value, long long* sl_size,
+                  long long* labels, double* prob);
+/* HOST memory, no stream.  sklearn's labelling_at_cut over a single-linkage tree of n_nodes points: merges below `cut`, clusters of
+ * fewer than min_cluster_size points are noise (-1), the rest numbered by ascending union-find root. */
+int svae_hdb_cut(long long n_nodes, const long long* left, const long long* right, const double* value, double cut,
+                 long long min_cluster_size, long long* labels);
+
 #ifdef __cplusplus
 }
 #endif

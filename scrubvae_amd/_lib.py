@@ -186,6 +186,12 @@ SIGNATURES = {
     "svae_gmm_chunks": (I, [I, I]),
     "svae_gmm_mstep_f64": (I, [P, I, I, I, I, I, P, D, P, P, P, P, P, P, P, P, P, P]),
     "svae_gmm_precision_f64": (I, [P, P, P, I, I, I, P, P, P, P]),
+    "svae_hdb_core": (I, [P, I, I, I, I, P, P]),
+    "svae_hdb_boruvka": (I, [P, I, I, I, P, P, P, D, I, P, P, P, P, P]),
+    "svae_hdb_relabel": (I, [P, I, P, P]),
+    "svae_hdb_merge": (I, [I, I, P, P, P, P, P, P, P, P, P]),
+    "svae_hdb_tree": (I, [I, P, P, P, I, I, I, D, LL, P, P, P, P, P, P]),
+    "svae_hdb_cut": (I, [LL, P, P, P, D, LL, P]),
 }
 
 _lib = None

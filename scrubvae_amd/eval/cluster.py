@@ -1,4 +1,4 @@
-"""Gaussian mixture clustering of latents on the device (reference: src/scrubvae/eval/cluster.py::gmm, and the fits of
+"""Clustering of latents on the device (reference: src/scrubvae/eval/cluster.py::gmm and ::dbscan, and the fits of
 eval/metrics.py::epoch_cluster_entropy).
 
     GaussianMixture(n_components=1, *, covariance_type="full", tol=1e-3, reg_covar=1e-6, max_iter=100,
@@ -469,3 +469,15 @@ def gmm(latents, n_components=25, covariance_type="full", random_state=None):
     the latents (reference cluster.py:51-66) -> (k_pred, model)."""
     return GaussianMixture(n_components=n_components, covariance_type=covariance_type, max_iter=150, init_params="k-means++",
                            reg_covar=1e-5, random_state=random_state, verbose=1).fit(latents)
+
+
+def dbscan(latents, eps=0.1, min_samples=500, label="cluster", path="./results/"):
+    """HDBSCAN(min_cluster_size=min_samples).fit_predict(latents) on the device, the labels saved to {path}{label}_sc_pred.npy
+    (reference cluster.py:69-87; eps is unused there too)."""
+    from .hdbscan import HDBSCAN
+    preds_path = "{}{}_sc_pred.npy".format(path, label)
+    print("Calculating sklearn dbscan clusters ...")
+    k_pred = HDBSCAN(min_cluster_size=min_samples).fit_predict(latents)
+    print(len(np.unique(k_pred)))
+    np.save(preds_path, k_pred)
+    return k_pred
