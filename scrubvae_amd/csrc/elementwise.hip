@@ -626,9 +626,12 @@ __global__ __launch_bounds__(256) void heads_diag_bwd_kernel(const float* __rest
 }
 
 // -------------------------------------------------------------------------- optimizer
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                    float* __restrict__ v, long long n, float lr, float b1, float b2, float eps,
-                                                    float wd, float step_size, float inv_bc2_sqrt, int decoupled, float gscale) {
+// The Adam / AdamW pass over one span, compiled ONCE (noinline) and called by both kernels below, so that the host-scalar and the
+// device-hyper path run the same instructions.  As two kernels with the same source lines the compiler fused different
+// multiply-adds in each, and an eager and a captured step differed in the last bit of p and v.
+__device__ __noinline__ void adam_span(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                         float* __restrict__ v, long long n, float lr, float b1, float b2, float eps,
+                                         float wd, float step_size, float inv_bc2_sqrt, int decoupled, float gscale) {
   const long long n4 = n / 4;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
     float4 pv = ld4(p + i * 4), gv = ld4(g + i * 4), mv = ld4(m + i * 4), vv = ld4(v + i * 4);
@@ -650,31 +653,18 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
   }
 }
 
+__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                    float* __restrict__ v, long long n, float lr, float b1, float b2, float eps,
+                                                    float wd, float step_size, float inv_bc2_sqrt, int decoupled, float gscale) {
+  adam_span(p, g, m, v, n, lr, b1, b2, eps, wd, step_size, inv_bc2_sqrt, decoupled, gscale);
+}
+
 // hipGraph-safe variant: the step-dependent scalars (lr, lr/bias_correction1, 1/sqrt(bias_correction2))
 // live in device memory and are refreshed by the host before each replay
 __global__ __launch_bounds__(256) void adam_kernel_dev(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                         float* __restrict__ v, long long n, const float* __restrict__ hyper,
                                                         float b1, float b2, float eps, float wd, int decoupled, float gscale) {
-  const float lr = hyper[0], step_size = hyper[1], inv_bc2_sqrt = hyper[2];
-  const long long n4 = n / 4;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
-    float4 pv = ld4(p + i * 4), gv = ld4(g + i * 4), mv = ld4(m + i * 4), vv = ld4(v + i * 4);
-    float pp[4] = {pv.x, pv.y, pv.z, pv.w}, gg[4] = {gv.x, gv.y, gv.z, gv.w}, mm[4] = {mv.x, mv.y, mv.z, mv.w},
-          vq[4] = {vv.x, vv.y, vv.z, vv.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      float gk = gg[k] * gscale;
-      if (decoupled) pp[k] *= (1.f - lr * wd);
-      else if (wd != 0.f) gk += wd * pp[k];
-      mm[k] = b1 * mm[k] + (1.f - b1) * gk;
-      vq[k] = b2 * vq[k] + (1.f - b2) * gk * gk;
-      const float denom = sqrtf(vq[k]) * inv_bc2_sqrt + eps;
-      pp[k] -= step_size * mm[k] / denom;
-    }
-    st4(p + i * 4, make_float4(pp[0], pp[1], pp[2], pp[3]));
-    st4(m + i * 4, make_float4(mm[0], mm[1], mm[2], mm[3]));
-    st4(v + i * 4, make_float4(vq[0], vq[1], vq[2], vq[3]));
-  }
+  adam_span(p, g, m, v, n, hyper[0], b1, b2, eps, wd, hyper[1], hyper[2], decoupled, gscale);
 }
 
 // Device-side step counter for captured (hipGraph) optimizer steps: hyper = {lr, lr / bias_correction1, 1 / sqrt(bias_correction2),

@@ -447,7 +447,7 @@ extern "C" int svae_tc_bwd(const float* z, int ldz, const float* mu, int ldm, co
                            const float* lse_l, const float* lse_a, float weight, float* d_mu, int ldd, float* d_lv, int ldv,
                            const float* sigma, int lds, void* stream) {
   SVAE_REQUIRE(z && mu && lv && lse_l && lse_a && d_mu && d_lv && batch > 0 && zdim > 0 && zdim <= 32 * TC_MAXCH, SVAE_ERR_ARG,
-               "tc_bwd: bad args");
+               "tc_bwd: bad args (z_dim must be <= %d)", 32 * TC_MAXCH);
   hipLaunchKernelGGL(tc_bwd_kernel, dim3(batch), dim3(256), 0, (hipStream_t)stream, z, ldz, mu, ldm, lv, batch, zdim, lse_l, lse_a,
                      weight, d_mu, ldd, d_lv, ldv, sigma, lds);
   return check_launch("tc_bwd");
