@@ -256,7 +256,8 @@ extern "C" int svae_inv_kin(const float* pose, const float* unit_offset_host, co
     for (int k = 0; k < 3; ++k) g.uoff[j][k] = unit_offset_host[3 * j + k];
   const int n_waves = tree->n_chains >= 2 ? tree->n_chains : 2;
   const int J3 = 3 * g.J, J6 = 6 * g.J;
-  const size_t smem = (size_t)64 * (2 * (J3 | 1) + (J6 | 1)) * sizeof(float);
+  const size_t smem = (size_t)64 * (2 * (J3 | 1) + (J6 | 1)) * sizeof(float);  // 70,912 B at J = 23, 99,072 B at SVAE_MAX_JOINTS
+  SVAE_REQUIRE(smem <= 160 * 1024, SVAE_ERR_SHAPE, "inv_kin: LDS tiles %zu B exceed 160 KiB", smem);
   hipLaunchKernelGGL(inv_kin_kernel, dim3((unsigned)((frames + 63) / 64)), dim3(64 * n_waves), smem, (hipStream_t)stream, g);
   return check_launch("inv_kin");
 }
