@@ -633,6 +633,22 @@ int svae_hdb_tree(int n, const int* lo, const int* hi, const double* w, int min_
 int svae_hdb_cut(long long n_nodes, const long long* left, const long long* right, const double* value, double cut,
                  long long min_cluster_size, long long* labels);
 
+/* ------------------------------------------------------- Maximum mean discrepancy between latent sets (csrc/mmd.hip) --- */
+/* The reference's eval/metrics.py::mmd_estimate, fp64.  Z [n][ld] = the rows of X (nx) then of Y (ny) converted to fp64, not centred;
+ * the pairs are i < j of Z, M = n (n - 1) / 2 of them.  Squared distance s as for HDBSCAN above (feature order, no FMA), dist = sqrt(s):
+ * scipy's pdist / cdist.  Nothing of size n^2 is stored; every result is bit-reproducible.  Any d >= 1, n < 2^26. */
+#define SVAE_MMD_WORK_WORDS 8256
+/* number of blocks of the all-pairs launches at n rows: svae_mmd_sums needs part [3 * blocks] */
+long long svae_mmd_blocks(int n);
+/* hm[0] = med = np.median of the M distances (the value of rank M / 2 for odd M, the mean of ranks M / 2 - 1 and M / 2 for even M),
+ * hm[1] = h = med * med.  Exact: a radix select over the bits of s, 5 all-pairs passes (6 for even M) enqueued back to back, no host
+ * round trip.  work [SVAE_MMD_WORK_WORDS] device scratch, initialised here. */
+int svae_mmd_select(const double* Z, int ld, int d, int n, unsigned long long* work, double* hm, void* stream);
+/* out = {kxx, kyy, kxy, kxx + kyy - 2 kxy}: means of exp((-(dist * dist)) / h[0]) over the pairs inside X, inside Y and across
+ * (nx >= 2, n - nx >= 2), h a device pointer (hm + 1 of svae_mmd_select, or a given bandwidth).  One all-pairs pass; per-block
+ * partial sums in part [3 * svae_mmd_blocks(n)] reduced in a fixed order. */
+int svae_mmd_sums(const double* Z, int ld, int d, int n, int nx, const double* h, double* part, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,6 +6,8 @@ variable from the latents, on the device.
     log_class_rand_cv(z, y_true, window=51, folds=5)  accuracy of elastic-net one-vs-rest logistic regression
     qda_rand_cv(z, y_true, window=51, folds=5)        accuracy of QuadraticDiscriminantAnalysis()
 
+    lda_rand_cv(z, y_true, window=51, folds=5)        accuracy of LinearDiscriminantAnalysis()
+
 Each returns a list of `folds` floats in fold order, as the reference's `rand_cv` wrapper does: rows z[0::window], then
 KFold(n_splits=folds, shuffle=True, random_state=100), restated here in numpy (this module does not import sklearn).  After the
 downsample every pass over the rows, every factorisation and every solver iteration runs in csrc/decode.hip (fp64) or, for the
@@ -22,10 +24,32 @@ Differences from the reference, by design:
     direction is left out of the class density (sklearn divides by its zero variance).
   - log_class_rand_cv fits, per fold, the classes present in that fold's training rows (sklearn's classes_); a class absent
     there is never predicted in that fold.
+  - lda_rand_cv raises the ValueErrors of qda_rand_cv, also for a class with a single training row (sklearn's LDA accepts one).
 Limits (ValueError): z_dim <= 128, <= 8 regression targets, <= 64 classes, <= 10 folds.
+
+The rest of the reference's eval/metrics.py:
+
+    mmd_estimate(X, Y, h=None)   maximum mean discrepancy of two sets of rows, squared-exponential kernel (metrics.py:332-374)
+    mmd_bandwidth(X, Y)          the h that mmd_estimate uses when h is None: the squared median of all pairwise distances
+    hungarian_match(x1, x2)      x1 relabelled with the labels of x2 that a maximum-weight assignment pairs them with (host)
+    shannon_entropy(x)           natural-log entropy of the label histogram (host)
+
+mmd_* take numpy arrays or torch tensors, host or device, any float dtype; the rows go to fp64 uncentred and everything runs in
+csrc/mmd.hip: the distances in scipy's pdist / cdist arithmetic, the median as an exact order statistic (mmd_bandwidth is
+bit-equal to the reference's np.median(...) ** 2), nothing of size n^2 stored, results bit-reproducible.  The sums are taken in
+a different order from numpy's, so mmd_estimate agrees with the reference to a few units of roundoff of kxx + kyy + 2 kxy.
+Differences from the reference, by design:
+  - mmd_*: ValueError for nx < 2 or ny < 2 (the reference returns nan with a numpy warning), for differing feature counts, for
+    non-finite rows and for an h that is not a finite positive number.  h is None with a zero median (more than half of all pairs
+    coincide) follows the arithmetic, -0 / 0: the result is nan, as in the reference.
+  - hungarian_match solves the assignment with its own rectangular Jonker-Volgenant solver (scipy is not a dependency); where
+    several assignments share the maximum, any of them is correct and the pick may differ from scipy's.
+  - the reference's shannon_entropy_torch is broken (it multiplies by x, not by the histogram) and unused: left out.
 """
 from __future__ import annotations
 
+import math
+import time
 import warnings
 
 import numpy as np
@@ -273,6 +297,66 @@ def qda_rand_cv(z, y_true, window=51, folds=5):
     return _qda(z, y_true, window, folds)
 
 
+def _lda(z, y_true, window, folds, want_rows=False):
+    dev = _device_of(z)
+    with torch.cuda.device(dev):
+        x = _rows(z, window, dev)
+        n, d = x.shape
+        classes, cls = _labels(y_true, window)
+        K = len(classes)
+        _check_dims(n, d, folds, k=K)
+        if K < 2:
+            raise ValueError(f"The number of classes has to be greater than one; got {K} class")
+        fold = kfold_assign(n, folds)
+        R = _Rows(x, fold, cls, K, None, dev)
+        F = R.folds
+        cnt_fc = (R.ghi - R.glo).reshape(F, K)
+        train_cnt = cnt_fc.sum(0)[None, :] - cnt_fc
+        if (train_cnt == 1).any():
+            f, c = np.argwhere(train_cnt == 1)[0]
+            raise ValueError(f"y has only 1 sample in class {classes[c]} (training set of fold {f}), covariance is ill defined.")
+        if ((train_cnt > 0).sum(1) < 2).any():
+            raise ValueError("a training fold holds fewer than two classes")
+        D = d + 1
+        T = _train_blocks(R.moments(D, R.glo, R.ghi), F, K).reshape(F * K, D, D)
+        cnt = T[:, d, d].clamp(min=2.0)
+        sx = T[:, :d, d]
+        mu = (sx / cnt[:, None]).contiguous()
+        # pooled within-class scatter of each training fold over n_train - (classes present); an absent class adds zeros
+        scatter = (T[:, :d, :d] - sx[:, :, None] * sx[:, None, :] / cnt[:, None, None]).view(F, K, d, d)
+        pooled = scatter[:, 0].clone()
+        for c in range(1, K):
+            pooled += scatter[:, c]
+        dof = train_cnt.sum(1) - (train_cnt > 0).sum(1)
+        if (dof < 1).any():
+            raise ValueError("a training fold holds no more rows than classes")
+        cov = pooled / torch.as_tensor(dof, dtype=torch.float64, device=dev)[:, None, None]
+        L, _, _, _ = spd_factor_solve(cov)
+        LK = L[:, None].expand(F, K, d, d).contiguous()  # one factor per fold: its logdet is the same for every class and drops out
+        with np.errstate(divide="ignore"):
+            logprior = np.log(train_cnt / train_cnt.sum(1, keepdims=True)).reshape(-1)
+        cst = torch.as_tensor(logprior, device=dev).contiguous()
+        correct = torch.zeros(F, dtype=torch.int32, device=dev)
+        pred = torch.empty(n, dtype=torch.int32, device=dev) if want_rows else None
+        gap = torch.empty(n, dtype=torch.float64, device=dev) if want_rows else None
+        check(_lib.lib().svae_cv_qda_score(R.A.data_ptr(), R.lda, d, K, R.flo_d.data_ptr(), R.fhi_d.data_ptr(), F, R.max_fold,
+                                           mu.data_ptr(), LK.data_ptr(), d, cst.data_ptr(), R.cls_d.data_ptr(), correct.data_ptr(),
+                                           ops._p(pred), ops._p(gap), ops._stream()), "cv_qda_score")
+        acc = [float(c) / float(m) for c, m in zip(correct.cpu().numpy(), R.fhi - R.flo)]
+        if not want_rows:
+            return acc
+        out = dict(acc=acc, perm=R.perm, fold=R.fold, pred=np.empty(n, np.int64), gap=np.empty(n))
+        out["pred"][R.perm] = classes[pred.cpu().numpy()]
+        out["gap"][R.perm] = gap.cpu().numpy()
+        return out
+
+
+def lda_rand_cv(z, y_true, window=51, folds=5):
+    """Accuracy per fold of LinearDiscriminantAnalysis() (reference metrics.py:293-298): the class means and one pooled covariance
+    per training fold (within-class scatter over n_train - classes), priors = the class frequencies."""
+    return _lda(z, y_true, window, folds)
+
+
 def logreg_problems(cnt_fc):
     """The one-vs-rest problems sklearn fits on each training fold, from the per-(fold, class) row counts [F, K]: the classes
     present in the fold's training rows; two present classes make one binary problem with the second one positive.  Returns
@@ -486,3 +570,165 @@ def cluster_entropy(k_preds0, k_preds1, n_components):
             hist = np.histogram(k0[sel], bins=bins)[0] / sel.sum()
             entropy += np.nan_to_num(hist * np.log2(1 / hist)).sum()
     return float(entropy / n_components)
+
+
+def shannon_entropy(x):
+    """Natural-log Shannon entropy of the histogram of the labels x (reference metrics.py:377-381)."""
+    counts = np.unique(np.asarray(x), return_counts=True)[1]
+    hist = counts / counts.sum()
+    return (hist * np.log(1 / hist)).sum()
+
+
+def _contingency(x1, x2):
+    """counts [len(np.unique(x1)), len(np.unique(x2))] of the label pairs: what pandas.crosstab(x1, x2) holds"""
+    k1, i1 = np.unique(x1, return_inverse=True)
+    k2, i2 = np.unique(x2, return_inverse=True)
+    table = np.zeros((len(k1), len(k2)), dtype=np.int64)
+    np.add.at(table, (i1.reshape(-1), i2.reshape(-1)), 1)
+    return k1, k2, table
+
+
+def max_weight_assignment(weight):
+    """(row_ind, col_ind) of a maximum-weight assignment of min(rows, cols) pairs of a rectangular table, rows ascending: what
+    scipy's linear_sum_assignment(weight, maximize=True) solves.  Shortest augmenting paths with potentials (Jonker-Volgenant),
+    O(rows^2 cols); exact for integer tables.  Ties between optimal assignments are broken by the search order."""
+    w = np.asarray(weight, dtype=np.float64)
+    if w.ndim != 2:
+        raise ValueError(f"expected a 2-D table, got {w.ndim}-D")
+    if not np.isfinite(w).all():
+        raise ValueError("the table holds non-finite entries")
+    flip = w.shape[0] > w.shape[1]
+    cost = -(w.T if flip else w)  # rows <= columns: every row is assigned
+    nr, nc = cost.shape
+    u, v = np.zeros(nr), np.zeros(nc)
+    col_of, row_of = np.full(nr, -1), np.full(nc, -1)
+    for r in range(nr):
+        dist = np.full(nc, np.inf)        # shortest alternating path from row r to each column, in reduced costs
+        path = np.full(nc, -1)            # the row before each column on that path
+        in_rows, in_cols = np.zeros(nr, dtype=bool), np.zeros(nc, dtype=bool)
+        i, low, sink = r, 0.0, -1
+        while sink < 0:
+            in_rows[i] = True
+            red = low + cost[i] - u[i] - v
+            better = ~in_cols & (red < dist)
+            dist[better] = red[better]
+            path[better] = i
+            j = int(np.argmin(np.where(in_cols, np.inf, dist)))
+            low = dist[j]
+            in_cols[j] = True
+            if row_of[j] < 0:
+                sink = j
+            else:
+                i = row_of[j]
+        others = in_rows.copy()
+        others[r] = False
+        u[r] += low
+        u[others] += low - dist[col_of[others]]
+        v[in_cols] -= low - dist[in_cols]
+        j = sink
+        while True:  # augment along the path
+            i = path[j]
+            row_of[j] = i
+            col_of[i], j = j, col_of[i]
+            if i == r:
+                break
+    rows, cols = np.arange(nr), col_of
+    if flip:
+        rows, cols = cols, rows
+    order = np.argsort(rows, kind="stable")
+    return rows[order], cols[order]
+
+
+def hungarian_match(x1, x2):
+    """x1 with each label replaced by the label of x2 it is matched to (reference metrics.py:388-412): the contingency table of
+    the two sequences (rows np.unique(x1), columns np.unique(x2)), a maximum-weight assignment on it (max_weight_assignment;
+    where several share the maximum, any of them is correct), then the reference's relabelling with its quirks: labels of x1 left
+    unmatched (more row labels than column labels) stay as they are, and a search index past the matched labels is read as 0."""
+    x1, x2 = np.asarray(x1), np.asarray(x2)
+    k1, k2, table = _contingency(x1, x2)
+    row_ind, col_ind = max_weight_assignment(table)
+    row_k, col_v = k1[row_ind], k2[col_ind]
+    idx = np.searchsorted(row_k, x1)
+    idx[idx == len(row_k)] = 0
+    mask = row_k[idx] == x1
+    return np.where(mask, col_v[idx], x1)
+
+
+_MMD_CALLS = {"select": 0, "sums": 0}  # launches of svae_mmd_select / svae_mmd_sums by this process
+
+
+def _mmd_rows(A, name):
+    """[n, d] -> fp64 rows where they are (torch tensor or numpy), checked finite"""
+    if torch.is_tensor(A):
+        t = A.detach()
+        if t.dim() != 2:
+            raise ValueError(f"{name}: expected a 2-D array of rows, got {t.dim()}-D")
+        t = t.to(torch.float64)
+        finite = bool(torch.isfinite(t).all()) if t.numel() else True
+    else:
+        t = np.asarray(A)
+        if t.ndim != 2:
+            raise ValueError(f"{name}: expected a 2-D array of rows, got {t.ndim}-D")
+        t = np.ascontiguousarray(t, dtype=np.float64)
+        finite = bool(np.isfinite(t).all())
+    if not finite:
+        raise ValueError(f"{name} holds non-finite values")
+    return t
+
+
+def _mmd_device(X, Y, h, want_h, info=None):
+    """(h, [kxx, kyy, kxy, mmd]) on the device of X (or of Y, or the current one); want_h: stop after the bandwidth ([...] is None).
+    info (a dict) receives med and the synchronised host-clock times select_s and sums_s."""
+    x, y = _mmd_rows(X, "X"), _mmd_rows(Y, "Y")
+    nx, ny = x.shape[0], y.shape[0]
+    if nx < 2 or ny < 2:
+        raise ValueError(f"the MMD estimate needs at least 2 rows on each side, got {nx} and {ny}")
+    if x.shape[1] != y.shape[1] or x.shape[1] < 1:
+        raise ValueError(f"X and Y must share one feature count >= 1, got {x.shape[1]} and {y.shape[1]}")
+    if h is not None:
+        if isinstance(h, bool) or not isinstance(h, (int, float, np.integer, np.floating)) or not (math.isfinite(h) and h > 0):
+            raise ValueError(f"h must be a finite positive number, got {h!r}")
+    n, d = nx + ny, x.shape[1]
+    dev = _device_of(x if torch.is_tensor(x) and x.is_cuda else y)
+    with torch.cuda.device(dev):
+        lib = _lib.lib()
+        blocks = lib.svae_mmd_blocks(n)
+        Z = torch.cat([(a if torch.is_tensor(a) else torch.from_numpy(a)).to(dev) for a in (x, y)]).contiguous()
+        st = ops._stream()
+        hm = torch.full((2,), float("nan") if h is None else float(h), dtype=torch.float64, device=dev)  # med, h
+
+        def clock():
+            if info is not None:
+                torch.cuda.synchronize(dev)
+            return time.perf_counter()
+
+        t0 = clock()
+        if h is None:
+            work = torch.empty(_lib.MMD_WORK_WORDS, dtype=torch.int64, device=dev)
+            _MMD_CALLS["select"] += 1
+            check(lib.svae_mmd_select(Z.data_ptr(), d, d, n, work.data_ptr(), hm.data_ptr(), st), "mmd_select")
+        t1 = clock()
+        out = None
+        if not want_h:
+            part = torch.empty(3 * blocks, dtype=torch.float64, device=dev)
+            out = torch.empty(4, dtype=torch.float64, device=dev)
+            _MMD_CALLS["sums"] += 1
+            check(lib.svae_mmd_sums(Z.data_ptr(), d, d, n, nx, hm[1:].data_ptr(), part.data_ptr(), out.data_ptr(), st), "mmd_sums")
+        t2 = clock()
+        res = (hm if out is None else torch.cat([hm, out])).cpu().numpy()
+        if info is not None:
+            info.update(med=float(res[0]) if h is None else None, select_s=t1 - t0, sums_s=t2 - t1)
+        return float(res[1]), (None if out is None else res[2:])
+
+
+def mmd_bandwidth(X, Y):
+    """The bandwidth mmd_estimate(X, Y) uses: np.median of the pairwise distances inside X, inside Y and across, squared --
+    bit-equal to the reference's inline recipe (metrics.py:364-369)."""
+    return _mmd_device(X, Y, None, True)[0]
+
+
+def mmd_estimate(X, Y, h=None):
+    """Estimate of the maximum mean discrepancy between the distributions X [nx, d] and Y [ny, d] were drawn from, with the kernel
+    exp(-|a - b|^2 / h) (reference metrics.py:332-374; Gretton et al. 2012): mean kernel value over the pairs inside X, plus that
+    inside Y, minus twice that across.  h defaults to mmd_bandwidth(X, Y)."""
+    return float(_mmd_device(X, Y, h, False)[1][3])
