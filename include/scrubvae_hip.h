@@ -366,6 +366,28 @@ int svae_inv_kin(const float* pose, const float* unit_offset_host, const svae_tr
 int svae_speed_parts(const float* pose, const int* parts_host, const int* part_len_host, int n_parts, int W, int J,
                      float* out, long long windows, void* stream);
 
+/* ---- Training batches from a resident recording ----
+ * The two kernels above, reading their windows out of a raw recording pose [frames][J][3] that stays in device memory:
+ * batch row b is the recording's frames starts[b] .. starts[b]+window-1 (starts: DEVICE int64 [batch], each in
+ * [0, frames-window]; the kernels clamp a start outside that range into it, so they never read outside the recording).
+ * The outputs are written in batch layout -- x6d [batch][window][J][6]; offsets [batch][window][J][3], root [batch][window][3],
+ * heading [batch][2] (each may be NULL) -- and the gathered [batch][window][J][3] pose tensor is never materialised.  The
+ * arithmetic per frame and per window is svae_inv_kin's / svae_speed_parts' own code, so on the same windows the results are
+ * bit-identical; the yaw, centring and "midfwd" turn come from the row's own middle frame starts[b] + window/2.
+ * index: NULL or DEVICE int64 [batch], the dataset index of each row.  The identity root quaternion that svae_inv_kin gives
+ * frame 0 of its array goes to frame 0 of the row with index[b] == 0, wherever it sits in the batch (no row with index NULL).
+ * Rejections (SVAE_ERR_ARG for null pose / starts / x6d / out, else SVAE_ERR_SHAPE; nothing launched): window < 1 (W < 2 for the
+ * speeds), frames < window, batch < 0, and the joint / chain / part limits of the two entry points above.  batch == 0: no-op. */
+int svae_window_batch(const float* pose, long long frames, const long long* starts, const long long* index,
+                      const float* unit_offset_host, const svae_tree* tree, int window, int midfwd, int centre_root,
+                      int truncate_len, float* x6d, float* offsets, float* root, float* heading, long long batch,
+                      void* stream);
+/* out [batch][3] as svae_speed_parts; mean_host / std_host: HOST float[3] each or both NULL; given, out = (speed - mean) / std
+ * in fp32, in that order (the reference's in-place normalisation of avg_speed_3d). */
+int svae_window_speed_parts(const float* pose, long long frames, const long long* starts, const int* parts_host,
+                            const int* part_len_host, int n_parts, int W, int J, const float* mean_host,
+                            const float* std_host, float* out, long long batch, void* stream);
+
 /* ------------------------------------------------------------- MLP-ensemble scrubber heads --- */
 /* G2/G3/A1: MLPEnsemble (disentangle.py:583-632) = up to four small MLPs (Linear/ReLU chains of <= 3 Linears) on the same input,
  * as ONE launch forward and one (+ a reduction launch) backward; GRScrubber (:635-660) feeds it mu, AdvNetScrubber (:663-684)

@@ -140,6 +140,8 @@ SIGNATURES = {
     "svae_rot_loss": (I, [P, P, F, P, P, LL, P]),
     "svae_inv_kin": (I, [P, C.POINTER(F), C.POINTER(Tree), I, I, I, I, P, P, P, P, LL, P]),
     "svae_speed_parts": (I, [P, C.POINTER(I), C.POINTER(I), I, I, I, P, LL, P]),
+    "svae_window_batch": (I, [P, LL, P, P, C.POINTER(F), C.POINTER(Tree), I, I, I, I, P, P, P, P, LL, P]),
+    "svae_window_speed_parts": (I, [P, LL, P, C.POINTER(I), C.POINTER(I), I, I, I, C.POINTER(F), C.POINTER(F), P, LL, P]),
     "svae_heads_beta_fwd": (I, [P, I, P, P, P, I, P, I, I, I, P]),
     "svae_heads_beta_bwd": (I, [P, I, P, P, P, I, P, I, P, F, P, I, I, I, P]),
     "svae_rot_blocks": (I, [LL]),
