@@ -670,6 +670,18 @@ int svae_mmd_select(const double* Z, int ld, int d, int n, unsigned long long* w
  * (nx >= 2, n - nx >= 2), h a device pointer (hm + 1 of svae_mmd_select, or a given bandwidth).  One all-pairs pass; per-block
  * partial sums in part [3 * svae_mmd_blocks(n)] reduced in a fixed order. */
 int svae_mmd_sums(const double* Z, int ld, int d, int n, int nx, const double* h, double* part, double* out, void* stream);
+/* Permutation null of that statistic (csrc/mmd_null.hip).  Relabelling p puts nx of the n rows into "X": bits [n][words] packs the
+ * memberships, bit (p & 63) of bits[j][p >> 6] = 1 when row j is in X under p (words >= ceil(P / 64); the bits past P of a row's
+ * last used word must be 0).  out[p] = kxx + kyy - 2 kxy of the split p, the estimator of svae_mmd_sums: one all-pairs pass per
+ * chunk of SVAE_MMD_NULL_COLS permutations, the 64 x 64 kernel tiles multiplied with the label columns on the fp64 matrix cores,
+ * per-block partials in work reduced in a fixed order; out[p] depends on column p of bits alone and is bit-reproducible.
+ * 1 <= P <= SVAE_MMD_NULL_MAX. */
+#define SVAE_MMD_NULL_COLS 256
+#define SVAE_MMD_NULL_MAX 65536
+/* doubles of work that svae_mmd_null needs at n rows and P permutations (0 for n < 2 or a P out of range) */
+long long svae_mmd_null_blocks(int n, int P);
+int svae_mmd_null(const double* Z, int ld, int d, int n, int nx, const double* h, const unsigned long long* bits, int words, int P,
+                  double* work, double* out, void* stream);
 
 #ifdef __cplusplus
 }

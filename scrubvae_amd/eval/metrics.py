@@ -31,6 +31,10 @@ The rest of the reference's eval/metrics.py:
 
     mmd_estimate(X, Y, h=None)   maximum mean discrepancy of two sets of rows, squared-exponential kernel (metrics.py:332-374)
     mmd_bandwidth(X, Y)          the h that mmd_estimate uses when h is None: the squared median of all pairwise distances
+    mmd_permutation_test(X, Y, h=None, n_permutations=1000, seed=0, permutations=None)
+                                 is that statistic distinguishable from zero: its permutation null and p-value (not in the
+                                 reference, which stops at the number)
+    mmd_permutations(n, n_permutations, seed, device)   the relabellings mmd_permutation_test draws by default
     hungarian_match(x1, x2)      x1 relabelled with the labels of x2 that a maximum-weight assignment pairs them with (host)
     shannon_entropy(x)           natural-log entropy of the label histogram (host)
 
@@ -38,6 +42,10 @@ mmd_* take numpy arrays or torch tensors, host or device, any float dtype; the r
 csrc/mmd.hip: the distances in scipy's pdist / cdist arithmetic, the median as an exact order statistic (mmd_bandwidth is
 bit-equal to the reference's np.median(...) ** 2), nothing of size n^2 stored, results bit-reproducible.  The sums are taken in
 a different order from numpy's, so mmd_estimate agrees with the reference to a few units of roundoff of kxx + kyy + 2 kxy.
+mmd_permutation_test recomputes the statistic under P relabellings of the pooled rows in csrc/mmd_null.hip: the kernel values do
+not depend on the labels, so all P statistics are one product of the kernel matrix, generated tile by tile, with the n x P matrix
+of 0 / 1 labels on the fp64 matrix cores -- one all-pairs pass per 256 permutations instead of one per permutation.  The median
+bandwidth depends on the pooled distances only, so h=None costs one select.  pvalue = (1 + #{T_p >= T_0}) / (1 + P).
 Differences from the reference, by design:
   - mmd_*: ValueError for nx < 2 or ny < 2 (the reference returns nan with a numpy warning), for differing feature counts, for
     non-finite rows and for an h that is not a finite positive number.  h is None with a zero median (more than half of all pairs
@@ -654,7 +662,7 @@ def hungarian_match(x1, x2):
     return np.where(mask, col_v[idx], x1)
 
 
-_MMD_CALLS = {"select": 0, "sums": 0}  # launches of svae_mmd_select / svae_mmd_sums by this process
+_MMD_CALLS = {"select": 0, "sums": 0, "null": 0}  # launches of svae_mmd_select / svae_mmd_sums / svae_mmd_null by this process
 
 
 def _mmd_rows(A, name):
@@ -676,9 +684,8 @@ def _mmd_rows(A, name):
     return t
 
 
-def _mmd_device(X, Y, h, want_h, info=None):
-    """(h, [kxx, kyy, kxy, mmd]) on the device of X (or of Y, or the current one); want_h: stop after the bandwidth ([...] is None).
-    info (a dict) receives med and the synchronised host-clock times select_s and sums_s."""
+def _mmd_check(X, Y, h):
+    """the argument errors of mmd_*, before any device work -> the fp64 rows (x, y)"""
     x, y = _mmd_rows(X, "X"), _mmd_rows(Y, "Y")
     nx, ny = x.shape[0], y.shape[0]
     if nx < 2 or ny < 2:
@@ -688,6 +695,15 @@ def _mmd_device(X, Y, h, want_h, info=None):
     if h is not None:
         if isinstance(h, bool) or not isinstance(h, (int, float, np.integer, np.floating)) or not (math.isfinite(h) and h > 0):
             raise ValueError(f"h must be a finite positive number, got {h!r}")
+    return x, y
+
+
+def _mmd_device(X, Y, h, want_h, info=None, keep=None):
+    """(h, [kxx, kyy, kxy, mmd]) on the device of X (or of Y, or the current one); want_h: stop after the bandwidth ([...] is None).
+    info (a dict) receives med and the synchronised host-clock times select_s and sums_s; keep (a dict) receives the device
+    tensors Z (the stacked fp64 rows) and hm (med, h)."""
+    x, y = _mmd_check(X, Y, h)
+    nx, ny = x.shape[0], y.shape[0]
     n, d = nx + ny, x.shape[1]
     dev = _device_of(x if torch.is_tensor(x) and x.is_cuda else y)
     with torch.cuda.device(dev):
@@ -715,6 +731,8 @@ def _mmd_device(X, Y, h, want_h, info=None):
             _MMD_CALLS["sums"] += 1
             check(lib.svae_mmd_sums(Z.data_ptr(), d, d, n, nx, hm[1:].data_ptr(), part.data_ptr(), out.data_ptr(), st), "mmd_sums")
         t2 = clock()
+        if keep is not None:
+            keep.update(Z=Z, hm=hm)
         res = (hm if out is None else torch.cat([hm, out])).cpu().numpy()
         if info is not None:
             info.update(med=float(res[0]) if h is None else None, select_s=t1 - t0, sums_s=t2 - t1)
@@ -732,3 +750,144 @@ def mmd_estimate(X, Y, h=None):
     exp(-|a - b|^2 / h) (reference metrics.py:332-374; Gretton et al. 2012): mean kernel value over the pairs inside X, plus that
     inside Y, minus twice that across.  h defaults to mmd_bandwidth(X, Y)."""
     return float(_mmd_device(X, Y, h, False)[1][3])
+
+
+MMD_MAX_PERMUTATIONS = _lib.MMD_NULL_MAX  # the cap on n_permutations: 65 536 (2.4e-5 resolves a p-value of 1.5e-5)
+_MMD_NULL_LAUNCH = 1024                   # permutations per svae_mmd_null launch: bounds the partials and the label scratch
+
+
+class MMDPermutationResult:
+    """statistic (float), pvalue (float), null_distribution (numpy [P] fp64) and h (float): scipy's permutation_test names."""
+    __slots__ = ("statistic", "pvalue", "null_distribution", "h")
+
+    def __init__(self, statistic, pvalue, null_distribution, h):
+        self.statistic, self.pvalue, self.null_distribution, self.h = statistic, pvalue, null_distribution, h
+
+    def __repr__(self):
+        return (f"MMDPermutationResult(statistic={self.statistic!r}, pvalue={self.pvalue!r}, "
+                f"null_distribution=<{len(self.null_distribution)} values>, h={self.h!r})")
+
+
+def mmd_permutations(n, n_permutations, seed, device):
+    """[n_permutations, n] int64 on `device`, every row a uniformly drawn permutation of range(n): the argsort of uniform keys from
+    a torch.Generator on that device seeded with `seed`.  Reproducible for a given seed, torch build and device type."""
+    n, P = int(n), int(n_permutations)
+    if n < 1 or P < 1:
+        raise ValueError(f"mmd_permutations needs n >= 1 and n_permutations >= 1, got {n} and {P}")
+    device = torch.device(device)
+    g = torch.Generator(device=device)
+    g.manual_seed(int(seed))
+    return torch.rand(P, n, generator=g, device=device).argsort(dim=1)
+
+
+def _mmd_count(n_permutations):
+    if isinstance(n_permutations, bool) or not isinstance(n_permutations, (int, np.integer)):
+        raise ValueError(f"n_permutations must be an integer, got {n_permutations!r}")
+    if not 1 <= n_permutations <= MMD_MAX_PERMUTATIONS:
+        raise ValueError(f"n_permutations must lie in [1, {MMD_MAX_PERMUTATIONS}], got {n_permutations}")
+    return int(n_permutations)
+
+
+def _mmd_permutation_array(permutations, n):
+    """the shape and dtype errors of a given `permutations`, on the host -> an integer torch tensor [P, n] where it is"""
+    if torch.is_tensor(permutations):
+        t = permutations.detach()
+    else:
+        a = np.asarray(permutations)
+        t = torch.as_tensor(a if a.flags.writeable else a.copy())  # torch refuses to share a read-only array
+    if t.dim() != 2 or t.shape[1] != n or t.shape[0] < 1:
+        raise ValueError(f"permutations must be [P, n = {n}] with P >= 1, got shape {tuple(t.shape)}")
+    if t.dtype not in (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8):
+        raise ValueError(f"permutations must hold integers, got {t.dtype}")
+    _mmd_count(t.shape[0])
+    return t
+
+
+def _mmd_check_permutations(perms):
+    """ValueError unless every row of perms [P, n] (a torch tensor, checked where it lives) is a permutation of range(n)"""
+    n = perms.shape[1]
+    want = torch.arange(n, device=perms.device, dtype=perms.dtype)
+    for p0 in range(0, perms.shape[0], _MMD_NULL_LAUNCH):
+        ok = (perms[p0: p0 + _MMD_NULL_LAUNCH].sort(dim=1).values == want).all(dim=1)
+        if not bool(ok.all()):
+            raise ValueError(f"permutations[{p0 + int((~ok).nonzero()[0])}] is not a permutation of range({n})")
+
+
+def _mmd_label_bits(perms, nx):
+    """perms [P, n] int64 (torch, any device) -> [n, ceil(P / 64)] int64 whose bit (p & 63) of word p >> 6 in row j is 1 when j is
+    among perms[p, :nx] (the rows relabelled "X"); the bits past P are 0.  The layout svae_mmd_null reads."""
+    P, n = perms.shape
+    words = (P + 63) // 64
+    member = torch.zeros(words * 64, n, dtype=torch.int64, device=perms.device)
+    member[:P].scatter_(1, perms[:, :nx], 1)
+    weight = torch.tensor([1 << k for k in range(63)] + [-(1 << 63)], dtype=torch.int64, device=perms.device)  # bit 63: the sign
+    return (member.view(words, 64, n) * weight.view(1, 64, 1)).sum(1).t().contiguous()
+
+
+def _mmd_null_device(Z, hm, nx, perms, info=None):
+    """T_p [P] fp64 on the device of Z (the stacked fp64 rows, the first nx of them X) for the checked relabellings perms [P, n]
+    (int64, same device), hm = (med, h) on the device.  info (a dict) receives the synchronised host-clock times pack_s (label
+    bits) and null_s (the svae_mmd_null launches)."""
+    dev = Z.device
+    n, d = Z.shape
+    P = perms.shape[0]
+    lib = _lib.lib()
+    st = ops._stream()
+    null = torch.empty(P, dtype=torch.float64, device=dev)
+    work = torch.empty(lib.svae_mmd_null_blocks(n, min(P, _MMD_NULL_LAUNCH)), dtype=torch.float64, device=dev)
+    pack_s = null_s = 0.0
+
+    def clock():
+        if info is not None:
+            torch.cuda.synchronize(dev)
+        return time.perf_counter()
+
+    for p0 in range(0, P, _MMD_NULL_LAUNCH):
+        count = min(_MMD_NULL_LAUNCH, P - p0)
+        t0 = clock()
+        bits = _mmd_label_bits(perms[p0: p0 + count], nx)
+        t1 = clock()
+        _MMD_CALLS["null"] += 1
+        check(lib.svae_mmd_null(Z.data_ptr(), d, d, n, nx, hm[1:].data_ptr(), bits.data_ptr(), bits.shape[1], count, work.data_ptr(),
+                                null[p0:].data_ptr(), st), "mmd_null")
+        t2 = clock()
+        pack_s, null_s = pack_s + (t1 - t0), null_s + (t2 - t1)
+    if info is not None:
+        info.update(pack_s=pack_s, null_s=null_s)
+    return null
+
+
+def mmd_permutation_test(X, Y, h=None, n_permutations=1000, seed=0, permutations=None):
+    """Permutation test of the hypothesis that X [nx, d] and Y [ny, d] come from one distribution, with mmd_estimate(X, Y, h) as
+    the statistic (the kernel two-sample test of Gretton et al. 2012) -> MMDPermutationResult.
+
+    statistic is mmd_estimate(X, Y, h), bit for bit.  null_distribution[p] is the same estimator after relabelling p of the pooled
+    rows Z = [X; Y]: the rows permutations[p, :nx] of Z become X, the rest Y.  pvalue = (1 + #{p: null[p] >= statistic}) / (1 + P),
+    compared in fp64.  h defaults to mmd_bandwidth(X, Y), which no relabelling changes; with a zero median the statistic, the
+    p-value and the null are nan, as in mmd_estimate.
+
+    permutations: [P, n] integers, numpy or torch; every row must be a permutation of range(n) (ValueError otherwise; the rows
+    are checked on the device before the null is computed).  When it is None, P = n_permutations rows are drawn by
+    mmd_permutations(n, n_permutations, seed, device): the result equals the call with those permutations bit for bit.
+    1 <= P <= MMD_MAX_PERMUTATIONS = 65 536.  Inputs and argument errors otherwise as for mmd_estimate."""
+    x, y = _mmd_check(X, Y, h)
+    nx, n, d = x.shape[0], x.shape[0] + y.shape[0], x.shape[1]
+    perms = None
+    if permutations is None:
+        P = _mmd_count(n_permutations)
+    else:
+        perms = _mmd_permutation_array(permutations, n)
+        P = perms.shape[0]
+    dev = _device_of(x if torch.is_tensor(x) and x.is_cuda else y)
+    with torch.cuda.device(dev):
+        if perms is None:
+            perms = mmd_permutations(n, P, seed, dev)
+        else:
+            perms = perms.to(device=dev, dtype=torch.int64)
+            _mmd_check_permutations(perms)
+        keep = {}
+        hv, out = _mmd_device(x, y, h, False, keep=keep)
+        null = _mmd_null_device(keep["Z"], keep["hm"], nx, perms).cpu().numpy()
+    statistic = float(out[3])
+    pvalue = float("nan") if math.isnan(statistic) else (1 + int((null >= statistic).sum())) / (1 + P)
+    return MMDPermutationResult(statistic, pvalue, null, hv)

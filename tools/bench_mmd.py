@@ -4,12 +4,20 @@ bandwidth select and the kernel sums, at nx in --sizes for z in --zs.  With --re
 cdist, np.median, np.exp) on at most 16 host threads at the sizes in --ref-sizes, in a child process ended after --ref-cap
 seconds.  Prints one JSON line.
 
-    python tools/bench_mmd.py [--reference] [--ref-sizes 4096,8192] [--ref-cap 600] [--sizes 4096,...,65536] [--zs 32,128]"""
+With --permutations P[,P...], the permutation null of mmd_permutation_test (csrc/mmd_null.hip) instead, with h given: the device
+time of the svae_mmd_null launches and of the label bit-packing at each size, the fp64 rate of the label products (2 flops per
+pair i < j and permutation; `executed` counts the whole 64 x 64 tiles and 256-column chunks the matrix cores run), and the ratio
+to the only other route to the null, P calls of mmd_estimate(Zp[:nx], Zp[nx:], h) on relabelled rows: at most 16 of them are
+timed and scaled to P.
+
+    python tools/bench_mmd.py [--reference] [--ref-sizes 4096,8192] [--ref-cap 600] [--sizes 4096,...,65536] [--zs 32,128]
+    python tools/bench_mmd.py --permutations 256,1024 --sizes 4096,16384 --zs 32"""
 import argparse
 import json
 import os
 import subprocess
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -31,6 +39,38 @@ def device_call(x, y):
     h, terms = M._mmd_device(x, y, None, False, info)
     return dict(select_s=round(info["select_s"], 5), sums_s=round(info["sums_s"], 5),
                 total_s=round(info["select_s"] + info["sums_s"], 5), h=h, mmd=float(terms[3]))
+
+
+LOOP_CALLS = 16
+
+
+def null_call(x, y, P, seed=0):
+    """x, y on the device, nx = ny rows"""
+    nx, n = x.shape[0], x.shape[0] + y.shape[0]
+    keep = {}
+    h, _ = M._mmd_device(x, y, None, False, keep=keep)
+    Z, hm = keep["Z"], keep["hm"]
+    perms = M.mmd_permutations(n, P, seed, x.device)
+    M._mmd_null_device(Z, hm, nx, perms[:1])  # this size's first launch
+    info = {}
+    null = M._mmd_null_device(Z, hm, nx, perms, info)
+    calls = min(LOOP_CALLS, P)
+    loop = []
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for p in range(calls):
+        Zp = Z[perms[p]]
+        loop.append(M.mmd_estimate(Zp[:nx], Zp[nx:], h))
+    torch.cuda.synchronize()
+    loop_s = (time.perf_counter() - t0) / calls * P
+    nt, chunks = (n + 63) // 64, (P + 255) // 256
+    useful = 2.0 * (n * (n - 1) // 2) * P
+    executed = 2.0 * 4096 * (nt * (nt + 1) // 2) * chunks * 256
+    null_h = null[:calls].cpu().numpy()
+    return dict(permutations=P, null_s=round(info["null_s"], 5), pack_s=round(info["pack_s"], 5),
+                tflops_useful=round(useful / info["null_s"] / 1e12, 2), tflops_executed=round(executed / info["null_s"] / 1e12, 2),
+                loop_s=round(loop_s, 4), loop_calls_timed=calls, speedup=round(loop_s / (info["null_s"] + info["pack_s"]), 1),
+                max_diff_to_loop=float(np.abs(null_h - np.array(loop)).max()), h=h)
 
 
 REF = """
@@ -67,10 +107,24 @@ def main():
     ap.add_argument("--reference", action="store_true")
     ap.add_argument("--ref-sizes", default="4096,8192")
     ap.add_argument("--ref-cap", type=float, default=600.0)
+    ap.add_argument("--permutations", default="", help="time the permutation null at these permutation counts instead")
     a = ap.parse_args()
     sizes = [int(s) for s in a.sizes.split(",") if s]
     zs = [int(z) for z in a.zs.split(",") if z]
     ref_sizes = [int(s) for s in a.ref_sizes.split(",") if s] if a.reference else []
+    if a.permutations:
+        counts = [int(p) for p in a.permutations.split(",") if p]
+        null_call(*(torch.from_numpy(t).cuda() for t in two_sets(256, zs[0])), 16)  # warm-up: code objects, torch kernels
+        out = dict(device=torch.cuda.get_device_name(0), calls=[])
+        for z in zs:
+            for n in sizes:
+                x, y = (torch.from_numpy(t).cuda() for t in two_sets(n, z))
+                for P in counts:
+                    row = dict(nx=n, ny=n, z=z, **null_call(x, y, P))
+                    out["calls"].append(row)
+                    print(json.dumps(row), file=sys.stderr, flush=True)
+        print(json.dumps(out))
+        return
     device_call(*(torch.from_numpy(t).cuda() for t in two_sets(min(sizes), zs[0])))  # warm-up: code objects, torch kernels
     out = dict(device=torch.cuda.get_device_name(0), calls=[])
     for z in zs:
