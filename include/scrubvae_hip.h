@@ -683,6 +683,27 @@ long long svae_mmd_null_blocks(int n, int P);
 int svae_mmd_null(const double* Z, int ld, int d, int n, int nx, const double* h, const unsigned long long* bits, int words, int P,
                   double* work, double* out, void* stream);
 
+/* ---------------------------------------------------------- Silhouette of a clustering of latents (csrc/silhouette.hip) --- */
+/* sklearn's silhouette_samples with the Euclidean metric, fp64.  Z [n][ld] fp64 rows, not centred; lab [n] = the cluster of each row
+ * in 0..K-1, count [K] = the rows of each cluster (every one >= 1), 2 <= K <= min(n - 1, SVAE_SIL_MAX_CLUSTERS), n < 2^26.  With
+ * S[i][c] = the sum over the rows j of cluster c of dist(i, j) (distances as for the MMD above):
+ *   a_i = S[i][own] / (m_own - 1), b_i = min over c != own of S[i][c] / m_c, nearest_i = that c (the lowest on an exact tie),
+ *   s_i = (b_i - a_i) / max(a_i, b_i); s_i = 0 where max(a_i, b_i) == 0; a_i = s_i = 0 for a row alone in its cluster.
+ * s, a, b, nearest [rows] receive the rows [row0, row0 + rows) against all n columns: one pass over rows x n distances per chunk of
+ * 256 clusters, the 64 x 64 distance tiles multiplied with the membership columns on the fp64 matrix cores, summed in a fixed
+ * order.  Nothing of size n^2 is stored; every result is bit-reproducible and does not depend on the numbering of the clusters. */
+#define SVAE_SIL_MAX_CLUSTERS 4096
+/* doubles of work that svae_silhouette needs for `rows` rows of n with K clusters (0 for n < 3, K < 2, K > SVAE_SIL_MAX_CLUSTERS,
+ * rows < 1 or rows > n): column chunks (at most 8, 1 once the grid holds 512 blocks) x rows padded to 64 x K padded to the
+ * 16, 64 or 256 cluster columns of a block */
+long long svae_silhouette_work(int rows, int n, int K);
+int svae_silhouette(const double* Z, int ld, int d, int n, const int* lab, const int* count, int K, int row0, int rows, double* work,
+                    double* s, double* a, double* b, int* nearest, void* stream);
+/* out[0] = the mean of v [n]: compensated sums at fixed positions, then a fixed tree */
+int svae_silhouette_mean(const double* v, long long n, double* out, void* stream);
+/* row[c] = the lowest row i of cluster c with the smallest a[i] (a [n] >= 0, finite): the medoid.  key [K] device scratch. */
+int svae_silhouette_medoids(const double* a, const int* lab, int n, int K, unsigned long long* key, long long* row, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -199,6 +199,10 @@ SIGNATURES = {
     "svae_mmd_sums": (I, [P, I, I, I, I, P, P, P, P]),
     "svae_mmd_null_blocks": (LL, [I, I]),
     "svae_mmd_null": (I, [P, I, I, I, I, P, P, I, I, P, P, P]),
+    "svae_silhouette_work": (LL, [I, I, I]),
+    "svae_silhouette": (I, [P, I, I, I, P, P, I, I, I, P, P, P, P, P, P]),
+    "svae_silhouette_mean": (I, [P, LL, P, P]),
+    "svae_silhouette_medoids": (I, [P, P, I, I, P, P, P]),
 }
 
 _lib = None
@@ -234,6 +238,7 @@ CV_MAX_DIM, CV_MAX_TARGETS, CV_MAX_CLASSES, CV_MAX_FOLDS, CV_MAX_GROUPS = 128, 8
 GMM_MAX_COMPONENTS, GMM_MAX_TRIALS = 64, 8  # include/scrubvae_hip.h SVAE_GMM_*
 MMD_WORK_WORDS = 8256  # include/scrubvae_hip.h SVAE_MMD_WORK_WORDS
 MMD_NULL_MAX = 65536  # include/scrubvae_hip.h SVAE_MMD_NULL_MAX
+SIL_MAX_CLUSTERS = 4096  # include/scrubvae_hip.h SVAE_SIL_MAX_CLUSTERS
 MAX_LOSS_TERMS = 48  # include/scrubvae_hip.h SVAE_MAX_LOSS_TERMS
 ERR_SHAPE, ERR_ALIGN, ERR_WORKSPACE, ERR_LAUNCH, ERR_ARG = -1, -2, -3, -4, -5  # include/scrubvae_hip.h svae_status
 

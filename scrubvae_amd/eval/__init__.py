@@ -3,3 +3,4 @@ from .eval import generative_restrictiveness  # noqa: F401
 from .hdbscan import HDBSCAN  # noqa: F401
 from .metrics import (cluster_entropy, hungarian_match, lda_rand_cv, linear_rand_cv, log_class_rand_cv, mlp_rand_cv,  # noqa: F401
                       mmd_bandwidth, mmd_estimate, mmd_permutation_test, mmd_permutations, qda_rand_cv, shannon_entropy)
+from .silhouette import cluster_medoids, cluster_silhouette, silhouette_samples, silhouette_score  # noqa: F401
