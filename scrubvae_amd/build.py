@@ -5,6 +5,8 @@ import sys
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 SOURCES = ["capi.hip", "gemm_f32.hip", "gemm_bf16s.hip", "halo_ws_bf16s.hip", "wgrad_bf16s.hip", "elementwise.hip", "pose_tail.hip", "latent.hip", "preprocess.hip", "ensemble.hip", "decode.hip", "gmm.hip", "hdbscan.hip", "mmd.hip", "mmd_null.hip", "silhouette.hip"]
+HEADERS = [os.path.join(CSRC, h) for h in ("svae_internal.h", "gemm_common.h", "split_common.h", "split_gather.h", "pair_tiles.h", "mmd_common.h")]
+HEADERS.append(os.path.join(CSRC, "..", "..", "include", "scrubvae_hip.h"))
 OUT = os.path.join(CSRC, "libscrubvae_hip.so")
 
 
@@ -12,9 +14,7 @@ def needs_build():
     if not os.path.exists(OUT):
         return True
     t = os.path.getmtime(OUT)
-    deps = [os.path.join(CSRC, s) for s in SOURCES + ["svae_internal.h", "gemm_common.h", "split_common.h", "split_gather.h", "pair_tiles.h"]]
-    deps.append(os.path.join(CSRC, "..", "..", "include", "scrubvae_hip.h"))
-    return any(os.path.getmtime(d) > t for d in deps)
+    return any(os.path.getmtime(d) > t for d in [os.path.join(CSRC, s) for s in SOURCES] + HEADERS)
 
 
 def build(force=False, verbose=False, ablation=False):
@@ -26,9 +26,7 @@ def build(force=False, verbose=False, ablation=False):
     from concurrent.futures import ThreadPoolExecutor
     objdir = os.path.join(CSRC, "build")
     os.makedirs(objdir, exist_ok=True)
-    headers = [os.path.join(CSRC, "svae_internal.h"), os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "split_common.h"), os.path.join(CSRC, "split_gather.h"), os.path.join(CSRC, "pair_tiles.h"),
-               os.path.join(CSRC, "..", "..", "include", "scrubvae_hip.h")]
-    hdr_t = max(os.path.getmtime(h) for h in headers)
+    hdr_t = max(os.path.getmtime(h) for h in HEADERS)
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"] + (["-DSVAE_ABLATION_KERNELS"] if ablation else [])
     tag = "_abl" if ablation else ""
 

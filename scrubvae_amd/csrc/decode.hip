@@ -515,17 +515,6 @@ __global__ __launch_bounds__(256) void cv_mse_grad_kernel(const float* const* __
   }
 }
 
-template <typename K>
-static int allow_lds(K kernel, DeviceOnce& once, const char* what) {
-  int dev;
-  if (once.need(&dev)) {
-    const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, CV_LDS_MAX);
-    SVAE_REQUIRE(e == hipSuccess, SVAE_ERR_LAUNCH, "%s: hipFuncSetAttribute: %s", what, hipGetErrorString(e));
-    once.done(dev);
-  }
-  return SVAE_OK;
-}
-
 static int lr_prob(LogregProb& pb, const double* A, int lda, int D, int n, const int* fold, const int* label, const int* pfold,
                    const int* pos, int P) {
   SVAE_REQUIRE(A && fold && label && pfold && pos && n > 0 && D >= 2 && D <= SVAE_CV_MAX_DIM + 1 && lda >= D && P >= 1 &&
@@ -537,7 +526,6 @@ static int lr_prob(LogregProb& pb, const double* A, int lda, int D, int n, const
 }  // namespace svae
 
 using namespace svae;
-#define ST(s) ((hipStream_t)(s))
 
 extern "C" int svae_cv_center(const float* x, int ldx, int d, const float* y, int ldy, int ny, const int* perm, int n, double* mean,
                               double* A, int lda, void* stream) {
@@ -567,7 +555,7 @@ extern "C" int svae_spd_factor_solve_f64(const double* M, int ldm, long long str
                SVAE_ERR_ARG, "spd_factor_solve_f64: bad args (n=%d batch=%d nrhs=%d)", n, batch, nrhs);
   const size_t smem = (size_t)(n * (n + 1) / 2 + n * (B ? nrhs : 0)) * sizeof(double);
   static DeviceOnce once;
-  if (int e = allow_lds(spd_factor_solve_kernel, once, "spd_factor_solve_f64")) return e;
+  if (int e = allow_lds(spd_factor_solve_kernel, once, CV_LDS_MAX, "spd_factor_solve_f64")) return e;
   hipLaunchKernelGGL(spd_factor_solve_kernel, dim3(batch), dim3(256), smem, ST(stream), M, ldm, strideM, n, B, B ? nrhs : 0, strideB, L, X,
                      logdet, rank, rtol);
   return check_launch("spd_factor_solve_f64");
@@ -590,7 +578,7 @@ extern "C" int svae_cv_qda_score(const double* A, int lda, int d, int K, const i
                    K <= SVAE_CV_MAX_CLASSES && folds >= 1 && folds <= SVAE_CV_MAX_FOLDS && max_rows > 0,
                SVAE_ERR_ARG, "cv_qda_score: bad args");
   static DeviceOnce once;
-  if (int e = allow_lds(cv_qda_kernel, once, "cv_qda_score")) return e;
+  if (int e = allow_lds(cv_qda_kernel, once, CV_LDS_MAX, "cv_qda_score")) return e;
   hipLaunchKernelGGL(cv_qda_kernel, dim3((max_rows + QDA_ROWS - 1) / QDA_ROWS, folds), dim3(QDA_ROWS), (size_t)d * QDA_ROWS * sizeof(double),
                      ST(stream), A, lda, d, K, lo, hi, mu, L, ldl, cst, label, correct, pred, gap);
   return check_launch("cv_qda_score");
@@ -617,7 +605,7 @@ extern "C" int svae_logreg_newton(const double* A, int lda, int D, int n, const 
                "logreg_newton: null buffer");
   LogregState st{W, dir, f0, delta, kkt, g0, done, iters};
   static DeviceOnce once;
-  if (int e = allow_lds(logreg_newton_kernel, once, "logreg_newton")) return e;
+  if (int e = allow_lds(logreg_newton_kernel, once, CV_LDS_MAX, "logreg_newton")) return e;
   hipLaunchKernelGGL(logreg_newton_kernel, dim3(P), dim3(64), (size_t)D * D * sizeof(double), ST(stream), pb, st, part,
                      (n + LR_ROWS - 1) / LR_ROWS, H, alpha, rho, tol, kkt_only, max_sweeps);
   return check_launch("logreg_newton");

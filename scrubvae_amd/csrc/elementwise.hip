@@ -834,7 +834,6 @@ __global__ __launch_bounds__(256) void double_softmax_ce_kernel(const float* __r
 }  // namespace svae
 
 using namespace svae;
-#define ST(s) ((hipStream_t)(s))
 
 extern "C" int svae_pack_input(const float* x6d, const float* root, const float* arena, float* x_in, long long rows,
                                int n_joints, int ld, void* stream) {

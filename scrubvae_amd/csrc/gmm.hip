@@ -377,7 +377,6 @@ static int mixture_args(const char* what, const double* A, int lda, int d, int n
 }  // namespace svae
 
 using namespace svae;
-#define ST(s) ((hipStream_t)(s))
 
 extern "C" int svae_gmm_kpp_blocks(int n) { return (n + KPP_ROWS - 1) / KPP_ROWS; }
 
@@ -406,12 +405,7 @@ extern "C" int svae_gmm_estep_f64(const double* A, int lda, int d, int n, int K,
                "gmm_estep_f64: bad args (d=%d ldp=%d)", d, ldp);
   const size_t smem = (size_t)d * ES_LDV * sizeof(double);
   static DeviceOnce once;
-  int dev;
-  if (once.need(&dev)) {
-    const hipError_t e = hipFuncSetAttribute((const void*)gmm_estep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    SVAE_REQUIRE(e == hipSuccess, SVAE_ERR_LAUNCH, "gmm_estep_f64: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    once.done(dev);
-  }
+  if (int e = allow_lds(gmm_estep_kernel, once, 96 * 1024, "gmm_estep_f64")) return e;
   hipLaunchKernelGGL(gmm_estep_kernel, dim3((n + ES_ROWS - 1) / ES_ROWS), dim3(ES_ROWS), smem, ST(stream), A, lda, d, n, K, diag, mu, P,
                      ldp, cst, resp, lpn, part, label, gap);
   return check_launch("gmm_estep_f64");

@@ -15,7 +15,7 @@
 #include <numeric>
 #include <vector>
 
-#include "pair_tiles.h"  // the staging helpers and #pragma clang fp contract(off)
+#include "pair_tiles.h"  // the tile walk and #pragma clang fp contract(off)
 
 namespace svae {
 
@@ -45,8 +45,7 @@ __global__ __launch_bounds__(256) void hdb_core_kernel(const double* __restrict_
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long r0 = (long long)blockIdx.x * HR;
   for (int e = threadIdx.x; e < HR * HHLD; e += 256) hist[e] = 0u;
-  const bool resident = hdb_rows_resident(X, ld, d, n, r0, qs);
-  const int nch = (d + HD - 1) / HD;
+  const PairRows rows = pair_rows(X, ld, d, n, r0, qs, cs);
   if (threadIdx.x < HR) {
     st_pref[lane] = 0ull;
     st_mask[lane] = 0ull;
@@ -61,9 +60,7 @@ __global__ __launch_bounds__(256) void hdb_core_kernel(const double* __restrict_
     const int shift = st_shift[lane], mode = st_mode[lane];
     for (long long c0 = 0; c0 < n; c0 += HT) {
       double s[HQ];
-#pragma unroll
-      for (int q = 0; q < HQ; ++q) s[q] = 0.0;
-      for (int ch = 0; ch < nch; ++ch) hdb_accumulate(hdb_stage(X, ld, d, n, r0, c0, ch, resident, qs, cs), cs, lane, wave, s);
+      pair_tile(rows, c0, s);
       if (mode != 2) {
 #pragma unroll
         for (int q = 0; q < HQ; ++q) {
@@ -140,8 +137,7 @@ __global__ __launch_bounds__(256) void hdb_boruvka_kernel(const double* __restri
   const int mycomp = ok ? comp[r] : -1;
   const unsigned myid = ok ? (unsigned)id[r] : 0u;
   double best = ok ? INFINITY : -INFINITY;
-  const bool resident = hdb_rows_resident(X, ld, d, n, r0, qs);
-  const int nch = (d + HD - 1) / HD;
+  const PairRows rows = pair_rows(X, ld, d, n, r0, qs, cs);
   unsigned long long bpk = ~0ull;
   for (long long c0 = 0; c0 < n; c0 += HT) {
     const double wm = wave_max_d(best);
@@ -156,14 +152,9 @@ __global__ __launch_bounds__(256) void hdb_boruvka_kernel(const double* __restri
       cid[threadIdx.x] = c < n ? id[c] : 0;
     }
     double s[HQ];
-#pragma unroll
-    for (int q = 0; q < HQ; ++q) s[q] = 0.0;
     const long long cw0 = c0 + wave * HQ;
     const bool live = cw0 < n && !(core[cw0] > wm);  // wave-uniform
-    for (int ch = 0; ch < nch; ++ch) {
-      const double* q = hdb_stage(X, ld, d, n, r0, c0, ch, resident, qs, cs);
-      if (live) hdb_accumulate(q, cs, lane, wave, s);
-    }
+    pair_tile(rows, c0, s, live);
     if (live && ok) {
 #pragma unroll
       for (int q = 0; q < HQ; ++q) {
@@ -288,37 +279,30 @@ struct CondRow {
 
 using namespace svae;
 
-#define ST(s) ((hipStream_t)(s))
-
 static unsigned grid(int n, int per) { return (unsigned)(((long long)n + per - 1) / per); }  // no int overflow up to n = 2^31 - 1
 
-static int rows_args(const char* what, const double* X, int ld, int d, int n) {
-  SVAE_REQUIRE(X && n >= 1 && d >= 1 && ld >= d, SVAE_ERR_ARG, "%s: bad rows (n=%d d=%d ld=%d)", what, n, d, ld);
-  return SVAE_OK;
-}
-
 extern "C" int svae_hdb_core(const double* X, int ld, int d, int n, int k, double* core, void* stream) {
-  if (int e = rows_args("hdb_core", X, ld, d, n)) return e;
+  if (int e = check_pair_rows("hdb_core", X, ld, d, n, 1)) return e;
   SVAE_REQUIRE(core && k >= 1 && k <= n, SVAE_ERR_ARG, "hdb_core: bad args (k=%d n=%d)", k, n);
   if (k == 1) {  // the row itself, at distance 0
     const hipError_t e = hipMemsetAsync(core, 0, sizeof(double) * (size_t)n, ST(stream));
     SVAE_REQUIRE(e == hipSuccess, SVAE_ERR_LAUNCH, "hdb_core: hipMemsetAsync: %s", hipGetErrorString(e));
     return SVAE_OK;
   }
-  hipLaunchKernelGGL(hdb_core_kernel, dim3(grid(n, HR)), dim3(256), 0, ST(stream), X, ld, d, n, k, core);
+  hipLaunchKernelGGL(hdb_core_kernel, dim3((unsigned)pair_tile_count(n)), dim3(256), 0, ST(stream), X, ld, d, n, k, core);
   return check_launch("hdb_core");
 }
 
 extern "C" int svae_hdb_boruvka(const double* X, int ld, int d, int n, const double* core, const int* id, const int* comp, double alpha,
                                 int n_comp, double* bw, unsigned long long* bp, unsigned long long* cw, unsigned long long* cp,
                                 void* stream) {
-  if (int e = rows_args("hdb_boruvka", X, ld, d, n)) return e;
+  if (int e = check_pair_rows("hdb_boruvka", X, ld, d, n, 1)) return e;
   SVAE_REQUIRE(core && id && comp && bw && bp && cw && cp && n_comp >= 2 && n_comp <= n && alpha > 0.0, SVAE_ERR_ARG,
                "hdb_boruvka: bad args (n=%d n_comp=%d alpha=%g)", n, n_comp, alpha);
   const unsigned rb = grid(n, 256);
   hipLaunchKernelGGL(hdb_comp_init_kernel, dim3(grid(n_comp, 256)), dim3(256), 0, ST(stream), cw, cp, n_comp);
   if (int e = check_launch("hdb_comp_init")) return e;
-  hipLaunchKernelGGL(hdb_boruvka_kernel, dim3(grid(n, HR)), dim3(256), 0, ST(stream), X, ld, d, n, core, id, comp, alpha,
+  hipLaunchKernelGGL(hdb_boruvka_kernel, dim3((unsigned)pair_tile_count(n)), dim3(256), 0, ST(stream), X, ld, d, n, core, id, comp, alpha,
                      bw, bp);
   if (int e = check_launch("hdb_boruvka")) return e;
   hipLaunchKernelGGL(hdb_comp_weight_kernel, dim3(rb), dim3(256), 0, ST(stream), bw, comp, n, cw);

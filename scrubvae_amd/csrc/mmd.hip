@@ -14,11 +14,10 @@
 
 #include <algorithm>
 
-#include "pair_tiles.h"  // the staging helpers and #pragma clang fp contract(off)
+#include "pair_tiles.h"  // the tile walk and #pragma clang fp contract(off)
+#include "mmd_common.h"  // mmd_value, mmd_statistic
 
 namespace svae {
-
-typedef unsigned long long u64;
 
 constexpr int MBITS = 13;            // digit width: 5 passes cover bits 62 .. 0 (shifts 50, 37, 24, 11, then the low 11 bits)
 constexpr int MBINS = 1 << MBITS;
@@ -30,29 +29,6 @@ static_assert(W_END <= SVAE_MMD_WORK_WORDS, "svae_mmd_select work buffer");
 
 __host__ __device__ inline int mmd_shift(int pass) { return pass < MPASSES - 1 ? 63 - MBITS * (pass + 1) : 0; }
 __host__ __device__ inline u64 mmd_digit_mask(int pass) { return pass < MPASSES - 1 ? (u64)(MBINS - 1) : (1ull << (63 - MBITS * (MPASSES - 1))) - 1ull; }
-
-// Block (x, y): row tile x against the column tiles [y ch, (y + 1) ch) that lie on or above the diagonal.
-struct Tiles {
-  long long r0;
-  int t_lo, t_hi;  // column tiles [t_lo, t_hi); empty when t_lo >= t_hi
-};
-__device__ __forceinline__ Tiles mmd_tiles(int n, int ch) {
-  const int nt = (n + HT - 1) / HT;
-  Tiles t;
-  t.r0 = (long long)blockIdx.x * HR;
-  t.t_lo = max((int)blockIdx.y * ch, (int)blockIdx.x);
-  t.t_hi = min(((int)blockIdx.y + 1) * ch, nt);
-  return t;
-}
-
-// squared distances of the block's rows to the 16 candidates of this wave in column tile ct
-__device__ __forceinline__ void mmd_tile(const double* __restrict__ Z, int ld, int d, int n, long long r0, long long c0, bool resident,
-                                         double* qs, double* cs, int lane, int wave, double (&s)[HQ]) {
-  const int nch = (d + HD - 1) / HD;
-#pragma unroll
-  for (int q = 0; q < HQ; ++q) s[q] = 0.0;
-  for (int ch = 0; ch < nch; ++ch) hdb_accumulate(hdb_stage(Z, ld, d, n, r0, c0, ch, resident, qs, cs), cs, lane, wave, s);
-}
 
 __global__ __launch_bounds__(256) void mmd_init_kernel(u64* __restrict__ work, u64 krem, u64 even) {
   for (int e = threadIdx.x; e < W_END; e += 256) work[e] = 0ull;
@@ -72,24 +48,23 @@ __global__ __launch_bounds__(256) void mmd_hist_kernel(const double* __restrict_
   __shared__ __attribute__((aligned(16))) double qs[HQCH * HD * HQLD];
   __shared__ __attribute__((aligned(16))) double cs[HT * HD];
   __shared__ unsigned hist[MBINS];
-  const Tiles t = mmd_tiles(n, ch);
+  const PairTileRange t = pair_upper_tiles(n, ch);
   if (t.t_lo >= t.t_hi) return;  // block-uniform
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const u64 pref = work[W_PREF], mask = work[W_MASK];
   const int shift = mmd_shift(pass);
   const u64 dmask = mmd_digit_mask(pass);
   for (int e = threadIdx.x; e < MBINS; e += 256) hist[e] = 0u;
-  const bool resident = hdb_rows_resident(Z, ld, d, n, t.r0, qs);
-  const long long i = t.r0 + lane;
+  const PairRows rows = pair_rows(Z, ld, d, n, t.r0, qs, cs);
+  const long long i = t.r0 + rows.lane;
   int run_digit = -1;
   unsigned run = 0u;
   for (int ct = t.t_lo; ct < t.t_hi; ++ct) {
     const long long c0 = (long long)ct * HT;
     double s[HQ];
-    mmd_tile(Z, ld, d, n, t.r0, c0, resident, qs, cs, lane, wave, s);  // its first barrier also orders the zeroing of hist
+    pair_tile(rows, c0, s);  // its first barrier also orders the zeroing of hist
 #pragma unroll
     for (int q = 0; q < HQ; ++q) {
-      const long long c = c0 + wave * HQ + q;
+      const long long c = c0 + rows.wave * HQ + q;
       const u64 key = (u64)__double_as_longlong(s[q]);
       if (i < c && c < n && (key & mask) == pref) {
         const int digit = (int)((key >> shift) & dmask);
@@ -141,20 +116,19 @@ __global__ __launch_bounds__(256) void mmd_upper_kernel(const double* __restrict
   __shared__ __attribute__((aligned(16))) double qs[HQCH * HD * HQLD];
   __shared__ __attribute__((aligned(16))) double cs[HT * HD];
   __shared__ u64 r_le[256], r_gt[256];
-  const Tiles t = mmd_tiles(n, ch);
+  const PairTileRange t = pair_upper_tiles(n, ch);
   if (t.t_lo >= t.t_hi) return;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const u64 s_lo = work[W_PREF];
-  const bool resident = hdb_rows_resident(Z, ld, d, n, t.r0, qs);
-  const long long i = t.r0 + lane;
+  const PairRows rows = pair_rows(Z, ld, d, n, t.r0, qs, cs);
+  const long long i = t.r0 + rows.lane;
   u64 le = 0ull, gt = ~0ull;
   for (int ct = t.t_lo; ct < t.t_hi; ++ct) {
     const long long c0 = (long long)ct * HT;
     double s[HQ];
-    mmd_tile(Z, ld, d, n, t.r0, c0, resident, qs, cs, lane, wave, s);
+    pair_tile(rows, c0, s);
 #pragma unroll
     for (int q = 0; q < HQ; ++q) {
-      const long long c = c0 + wave * HQ + q;
+      const long long c = c0 + rows.wave * HQ + q;
       const u64 key = (u64)__double_as_longlong(s[q]);
       if (i < c && c < n) {
         if (key <= s_lo) ++le;
@@ -198,28 +172,25 @@ __global__ __launch_bounds__(256) void mmd_sums_kernel(const double* __restrict_
   __shared__ __attribute__((aligned(16))) double qs[HQCH * HD * HQLD];
   __shared__ __attribute__((aligned(16))) double cs[HT * HD];
   __shared__ double red[3 * 256];
-  const Tiles t = mmd_tiles(n, ch);
+  const PairTileRange t = pair_upper_tiles(n, ch);
   const long long block = (long long)blockIdx.y * gridDim.x + blockIdx.x;
   if (t.t_lo >= t.t_hi) {
     if (threadIdx.x < 3) part[3 * block + threadIdx.x] = 0.0;
     return;
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const double h = hp[0];
-  const bool resident = hdb_rows_resident(Z, ld, d, n, t.r0, qs);
-  const long long i = t.r0 + lane;
+  const PairRows rows = pair_rows(Z, ld, d, n, t.r0, qs, cs);
+  const long long i = t.r0 + rows.lane;
   double a[3] = {0.0, 0.0, 0.0};
   for (int ct = t.t_lo; ct < t.t_hi; ++ct) {
     const long long c0 = (long long)ct * HT;
     double s[HQ];
-    mmd_tile(Z, ld, d, n, t.r0, c0, resident, qs, cs, lane, wave, s);
+    pair_tile(rows, c0, s);
 #pragma unroll
     for (int q = 0; q < HQ; ++q) {
-      const long long c = c0 + wave * HQ + q;
+      const long long c = c0 + rows.wave * HQ + q;
       if (i < c && c < n) {
-        const double dist = sqrt(s[q]);
-        const double dd = dist * dist;
-        const double v = exp(-dd / h);
+        const double v = mmd_value(s[q], h);
         if (c < nx) a[0] = a[0] + v;
         else if (i >= nx) a[1] = a[1] + v;
         else a[2] = a[2] + v;
@@ -246,12 +217,7 @@ __global__ __launch_bounds__(1024) void mmd_reduce_kernel(const double* __restri
   double sum[3] = {0.0, 0.0, 0.0}, comp[3] = {0.0, 0.0, 0.0};
   for (long long b = threadIdx.x; b < blocks; b += 1024) {
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const double v = part[3 * b + k];
-      const double tsum = sum[k] + v;
-      comp[k] = comp[k] + (fabs(sum[k]) >= fabs(v) ? (sum[k] - tsum) + v : (v - tsum) + sum[k]);
-      sum[k] = tsum;
-    }
+    for (int k = 0; k < 3; ++k) neumaier_add(sum[k], comp[k], part[3 * b + k]);
   }
 #pragma unroll
   for (int k = 0; k < 3; ++k) red[k * 1024 + threadIdx.x] = sum[k] + comp[k];
@@ -262,36 +228,26 @@ __global__ __launch_bounds__(1024) void mmd_reduce_kernel(const double* __restri
       for (int k = 0; k < 3; ++k) red[k * 1024 + threadIdx.x] = red[k * 1024 + threadIdx.x] + red[k * 1024 + threadIdx.x + o];
     __syncthreads();
   }
-  if (threadIdx.x == 0) {
-    const double kxx = red[0] / ((double)nx * (double)(nx - 1) / 2.0);
-    const double kyy = red[1024] / ((double)ny * (double)(ny - 1) / 2.0);
-    const double kxy = red[2048] / ((double)nx * (double)ny);
-    out[0] = kxx;
-    out[1] = kyy;
-    out[2] = kxy;
-    out[3] = (kxx + kyy) - 2.0 * kxy;
-  }
+  if (threadIdx.x == 0) mmd_statistic(red[0], red[1024], red[2048], nx, ny, out);
 }
 
 }  // namespace svae
 
 using namespace svae;
 
-#define ST(s) ((hipStream_t)(s))
-
 // column tiles per block: enough blocks to fill the device at small n, long tile loops (rows staged once) at large n
 static int mmd_chunk(int n) {
-  const long long nt = ((long long)n + HT - 1) / HT;
+  const long long nt = pair_tile_count(n);
   return (int)std::min<long long>(MCH_MAX, std::max<long long>(1, nt * nt / 4096));
 }
 
 static dim3 mmd_grid(int n) {
-  const int nt = (int)(((long long)n + HT - 1) / HT), ch = mmd_chunk(n);
+  const int nt = pair_tile_count(n), ch = mmd_chunk(n);
   return dim3((unsigned)nt, (unsigned)((nt + ch - 1) / ch));
 }
 
 static int mmd_args(const char* what, const double* Z, int ld, int d, int n) {
-  SVAE_REQUIRE(Z && n >= 2 && d >= 1 && ld >= d, SVAE_ERR_ARG, "%s: bad rows (n=%d d=%d ld=%d)", what, n, d, ld);
+  if (int e = check_pair_rows(what, Z, ld, d, n, 2)) return e;
   SVAE_REQUIRE(mmd_grid(n).y <= 65535u, SVAE_ERR_ARG, "%s: n=%d rows exceed the tile grid", what, n);
   return SVAE_OK;
 }

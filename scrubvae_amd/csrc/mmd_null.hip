@@ -1,6 +1,6 @@
 // Permutation null of the MMD statistic of mmd.hip: T_p = kxx + kyy - 2 kxy of P relabellings of the pooled rows Z = [X; Y], fp64,
-// nothing of size n^2 stored.  The kernel values K_ij = exp((-(dist * dist)) / h) (pair_tiles.h distances, the exp expression of
-// mmd_sums_kernel) do not depend on the labels, so all P statistics come from one all-pairs pass: a block computes its 64 x 64
+// nothing of size n^2 stored.  The kernel values K_ij = mmd_value(s_ij, h) (mmd_common.h, shared with mmd_sums_kernel; pair_tiles.h
+// distances) do not depend on the labels, so all P statistics come from one all-pairs pass: a block computes its 64 x 64
 // tile of K (zero where i >= j or past n), lays it out in LDS as the A operand and multiplies it on the fp64 matrix cores
 // (v_mfma_f64_16x16x4_f64) with the tile's 64 x 256 label columns m_jp in {0, 1} (1: row j is in "X" under relabelling p),
 // expanded on the fly from packed bits [n][words].  U_ip = sum_j K_ij m_jp accumulates in registers over the block's column
@@ -19,23 +19,18 @@
 
 #include <algorithm>
 
-#include "pair_tiles.h"  // the staging helpers and #pragma clang fp contract(off)
+#include "pair_tiles.h"  // the tile walk, the A-operand tile and #pragma clang fp contract(off)
+#include "mmd_common.h"  // mmd_value, mmd_statistic
 
 namespace svae {
-
-typedef unsigned long long u64;
-typedef double double4_t __attribute__((ext_vector_type(4)));
 
 constexpr int NPC = SVAE_MMD_NULL_COLS;  // permutation columns per block (grid.z = chunks of them; K is recomputed per chunk)
 constexpr int NPW = NPC / 64;            // label words per row and chunk
 constexpr int NPT = NPC / 16;            // 16 x 16 result tiles per wave: 4 fp64 accumulators per lane each
 constexpr int NGY = 8;                   // column chunks per row tile at most: bounds the partials at 3 * 8 * (n / 64) * P doubles
 
-// dynamic LDS, in doubles
-constexpr int L_QS = 0;                          // the block's rows, resident (pair_tiles.h)
-constexpr int L_CS = L_QS + HQCH * HD * HQLD;    // candidates of the tile
-constexpr int L_KT = L_CS + HT * HD;             // kt[j][i]: the K tile, column-major; after the loop: red[3][4][NPC]
-constexpr int L_LB = L_KT + HT * HR;             // label words of the tile's columns [64][NPW]
+// dynamic LDS, in doubles, after the prefix of pair_tiles.h; kt holds the K tile and, after the loop, red[3][4][NPC]
+constexpr int L_LB = PAIR_LDS_END;               // label words of the tile's columns [64][NPW]
 constexpr int L_RB = L_LB + HT * NPW;            // label words of the block's rows [64][NPW]
 constexpr int L_RS = L_RB + HR * NPW;            // row sums [64]
 constexpr int L_END = L_RS + HR;
@@ -48,19 +43,16 @@ __global__ __launch_bounds__(256) void mmd_null_kernel(const double* __restrict_
                                                        const double* __restrict__ hp, const u64* __restrict__ bits, int words,
                                                        u64 flip, int ppad, double* __restrict__ part) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
-  double* qs = lds + L_QS;
-  double* cs = lds + L_CS;
-  double* kt = lds + L_KT;
+  double* kt = lds + PAIR_LDS_KT;
   u64* lb = reinterpret_cast<u64*>(lds + L_LB);
   u64* rb = reinterpret_cast<u64*>(lds + L_RB);
   double* rs = lds + L_RS;
-  const int nt = (n + HT - 1) / HT;
-  const long long r0 = (long long)blockIdx.x * HR;
-  const int t_lo = max((int)blockIdx.y * ch, (int)blockIdx.x), t_hi = min(((int)blockIdx.y + 1) * ch, nt);
+  const PairTileRange tr = pair_upper_tiles(n, ch);
+  const long long r0 = tr.r0;
   const long long blocks = (long long)gridDim.x * gridDim.y, block = (long long)blockIdx.y * gridDim.x + blockIdx.x;
   double* out = part + block * ppad + (long long)blockIdx.z * NPC + threadIdx.x;
   const long long kind = blocks * ppad;
-  if (t_lo >= t_hi) {  // block-uniform: below the diagonal
+  if (tr.t_lo >= tr.t_hi) {  // block-uniform: below the diagonal
     out[0] = 0.0;
     out[kind] = 0.0;
     out[2 * kind] = 0.0;
@@ -72,39 +64,28 @@ __global__ __launch_bounds__(256) void mmd_null_kernel(const double* __restrict_
   const int srow = threadIdx.x / NPW;
   const double h = hp[0];
   rb[threadIdx.x] = r0 + srow < n && wz < words ? bits[(r0 + srow) * words + wz] ^ flip : 0ull;
-  const bool resident = hdb_rows_resident(Z, ld, d, n, r0, qs);
+  const PairRows rows = pair_rows(Z, ld, d, n, r0, lds + PAIR_LDS_QS, lds + PAIR_LDS_CS);
   const long long i = r0 + lane;
-  const int nch = (d + HD - 1) / HD;
   double4_t acc[NPT];
 #pragma unroll
   for (int t = 0; t < NPT; ++t) acc[t] = double4_t{0.0, 0.0, 0.0, 0.0};
   double rsum = 0.0;
-  for (int ct = t_lo; ct < t_hi; ++ct) {
+  for (int ct = tr.t_lo; ct < tr.t_hi; ++ct) {
     const long long c0 = (long long)ct * HT;
     double s[HQ];
-#pragma unroll
-    for (int q = 0; q < HQ; ++q) s[q] = 0.0;
-    // the first barrier in here also ends the previous tile's reads of kt and lb
-    for (int c = 0; c < nch; ++c) hdb_accumulate(hdb_stage(Z, ld, d, n, r0, c0, c, resident, qs, cs), cs, lane, wave, s);
+    pair_tile(rows, c0, s);  // its first barrier also ends the previous tile's reads of kt and lb
 #pragma unroll
     for (int q = 0; q < HQ; ++q) {
       const long long c = c0 + wave * HQ + q;
-      double v = 0.0;
-      if (i < c && c < n) {
-        const double dist = sqrt(s[q]);
-        const double dd = dist * dist;
-        v = exp(-dd / h);
-      }
-      kt[(wave * HQ + q) * HR + lane] = v;
+      pair_kt_value(kt, lane, wave, q) = i < c && c < n ? mmd_value(s[q], h) : 0.0;
     }
     lb[threadIdx.x] = c0 + srow < n && wz < words ? bits[(c0 + srow) * words + wz] ^ flip : 0ull;
     __syncthreads();
-    // wave w: rows [16 w, 16 w + 16) of the tile x all NPC columns.  Lane l holds A[row l & 15][k = l >> 4] and
-    // B[k = l >> 4][col l & 15] of each 16 x 16 x 4 step; step ks covers the tile's columns j = 4 ks + k.
+    // wave w: rows [16 w, 16 w + 16) of the tile x all NPC columns (lane layouts: pair_tiles.h)
 #pragma unroll 2
     for (int ks = 0; ks < HT / 4; ++ks) {
       const int j = 4 * ks + kg;
-      const double a = kt[j * HR + 16 * wave + l16];
+      const double a = pair_kt_a(kt, j, wave, l16);
       rsum = rsum + a;
 #pragma unroll
       for (int w = 0; w < NPW; ++w) {
@@ -123,7 +104,7 @@ __global__ __launch_bounds__(256) void mmd_null_kernel(const double* __restrict_
   __syncthreads();  // every wave is done with kt
   if (kg == 0) rs[16 * wave + l16] = rsum;
   __syncthreads();
-  // C/D of the f64 form: lane l, register r holds [row (l >> 4) + 4 r][col l & 15]
+  // acc[t][r] is [row (l >> 4) + 4 r][col l & 15] of result tile t
 #pragma unroll
   for (int t = 0; t < NPT; ++t) {
     double sa = 0.0, sb = 0.0, sc = 0.0;
@@ -161,8 +142,7 @@ __global__ __launch_bounds__(256) void mmd_null_kernel(const double* __restrict_
 }
 
 // Block b: columns [16 b, 16 b + 16).  Thread (column c = t & 15, slot s = t >> 4) adds the partials of blocks s, s + 16, ... with a
-// compensated (Neumaier) sum, then a fixed tree over the 16 slots; the means and the statistic as mmd_reduce_kernel takes them
-// (na rows on the marked side, nb on the other).
+// compensated (Neumaier) sum, then a fixed tree over the 16 slots (na rows on the marked side, nb on the other).
 __global__ __launch_bounds__(256) void mmd_null_reduce_kernel(const double* __restrict__ part, long long blocks, int ppad, int P,
                                                               int na, int nb, double* __restrict__ out) {
   __shared__ double red[3 * 256];
@@ -171,12 +151,7 @@ __global__ __launch_bounds__(256) void mmd_null_reduce_kernel(const double* __re
   double sum[3] = {0.0, 0.0, 0.0}, comp[3] = {0.0, 0.0, 0.0};
   for (long long b = slot; b < blocks; b += 16) {
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const double v = part[(k * blocks + b) * ppad + p];
-      const double tsum = sum[k] + v;
-      comp[k] = comp[k] + (fabs(sum[k]) >= fabs(v) ? (sum[k] - tsum) + v : (v - tsum) + sum[k]);
-      sum[k] = tsum;
-    }
+    for (int k = 0; k < 3; ++k) neumaier_add(sum[k], comp[k], part[(k * blocks + b) * ppad + p]);
   }
 #pragma unroll
   for (int k = 0; k < 3; ++k) red[k * 256 + threadIdx.x] = sum[k] + comp[k];
@@ -187,28 +162,21 @@ __global__ __launch_bounds__(256) void mmd_null_reduce_kernel(const double* __re
       for (int k = 0; k < 3; ++k) red[k * 256 + threadIdx.x] = red[k * 256 + threadIdx.x] + red[k * 256 + threadIdx.x + 16 * o];
     __syncthreads();
   }
-  if (slot == 0 && p < P) {
-    const double kaa = red[threadIdx.x] / ((double)na * (double)(na - 1) / 2.0);
-    const double kbb = red[256 + threadIdx.x] / ((double)nb * (double)(nb - 1) / 2.0);
-    const double kab = red[512 + threadIdx.x] / ((double)na * (double)nb);
-    out[p] = (kaa + kbb) - 2.0 * kab;  // a, b = X, Y or Y, X: the same bits either way
-  }
+  if (slot == 0 && p < P) out[p] = mmd_statistic(red[threadIdx.x], red[256 + threadIdx.x], red[512 + threadIdx.x], na, nb, nullptr);
 }
 
 }  // namespace svae
 
 using namespace svae;
 
-#define ST(s) ((hipStream_t)(s))
-
 // column tiles per block: at most NGY blocks per row tile, so a block's accumulators see a long run of tiles at large n
 static int null_chunk(int n) {
-  const int nt = (int)(((long long)n + HT - 1) / HT), gy = std::min(nt, NGY);
+  const int nt = pair_tile_count(n), gy = std::min(nt, NGY);
   return (nt + gy - 1) / gy;
 }
 
 static dim3 null_grid(int n, int P) {
-  const int nt = (int)(((long long)n + HT - 1) / HT), ch = null_chunk(n);
+  const int nt = pair_tile_count(n), ch = null_chunk(n);
   return dim3((unsigned)nt, (unsigned)((nt + ch - 1) / ch), (unsigned)((P + NPC - 1) / NPC));
 }
 
@@ -220,17 +188,12 @@ extern "C" long long svae_mmd_null_blocks(int n, int P) {
 
 extern "C" int svae_mmd_null(const double* Z, int ld, int d, int n, int nx, const double* h, const unsigned long long* bits, int words,
                              int P, double* work, double* out, void* stream) {
-  SVAE_REQUIRE(Z && n >= 2 && n < (1 << 26) && d >= 1 && ld >= d, SVAE_ERR_ARG, "mmd_null: bad rows (n=%d d=%d ld=%d)", n, d, ld);
+  if (int e = check_pair_rows("mmd_null", Z, ld, d, n, 2, (1 << 26) - 1)) return e;
   SVAE_REQUIRE(h && bits && work && out && nx >= 2 && n - nx >= 2, SVAE_ERR_ARG, "mmd_null: bad args (n=%d nx=%d)", n, nx);
   SVAE_REQUIRE(P >= 1 && P <= SVAE_MMD_NULL_MAX && words >= (P + 63) / 64, SVAE_ERR_ARG, "mmd_null: bad permutation count (P=%d words=%d)",
                P, words);
   static DeviceOnce once;
-  int dev;
-  if (once.need(&dev)) {
-    const hipError_t e = hipFuncSetAttribute((const void*)mmd_null_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)NULL_LDS);
-    SVAE_REQUIRE(e == hipSuccess, SVAE_ERR_LAUNCH, "mmd_null: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    once.done(dev);
-  }
+  if (int e = allow_lds(mmd_null_kernel, once, (int)NULL_LDS, "mmd_null")) return e;
   const dim3 g = null_grid(n, P);
   const int ppad = (int)g.z * NPC;
   const bool flip = nx > n - nx;  // mark the smaller side

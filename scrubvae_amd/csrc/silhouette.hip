@@ -14,21 +14,15 @@
 
 #include <algorithm>
 
-#include "pair_tiles.h"  // the staging helpers and #pragma clang fp contract(off)
+#include "pair_tiles.h"  // the tile walk, the A-operand tile and #pragma clang fp contract(off)
 
 namespace svae {
-
-typedef unsigned long long u64;
-typedef double double4_t __attribute__((ext_vector_type(4)));
 
 constexpr int SIL_NGY = 8;        // column chunks per row tile at most
 constexpr int SIL_BLOCKS = 512;   // grid y splits the column tiles only while the grid holds fewer blocks than this
 
-// dynamic LDS, in doubles
-constexpr int S_QS = 0;                          // the block's rows, resident (pair_tiles.h)
-constexpr int S_CS = S_QS + HQCH * HD * HQLD;    // candidates of the tile
-constexpr int S_KT = S_CS + HT * HD;             // kt[j][i]: the distance tile, column-major
-constexpr int S_LB = S_KT + HT * HR;             // cluster of the tile's columns [64] int32, -1 past n
+// dynamic LDS, in doubles, after the prefix of pair_tiles.h; kt holds the distance tile
+constexpr int S_LB = PAIR_LDS_END;               // cluster of the tile's columns [64] int32, -1 past n
 constexpr int S_END = S_LB + HT / 2;
 constexpr size_t SIL_LDS = (size_t)S_END * sizeof(double);  // 74,496 B: two blocks per CU
 static_assert(SIL_LDS <= 160 * 1024, "LDS per workgroup");
@@ -39,44 +33,36 @@ __global__ __launch_bounds__(256) void sil_sums_kernel(const double* __restrict_
                                                        int row0, int ch, long long rpad, int kpad, double* __restrict__ part) {
   constexpr int NT = NC / 16;  // 16 x 16 result tiles per wave: 4 fp64 accumulators per lane each
   extern __shared__ __attribute__((aligned(16))) double lds[];
-  double* qs = lds + S_QS;
-  double* cs = lds + S_CS;
-  double* kt = lds + S_KT;
+  double* kt = lds + PAIR_LDS_KT;
   int* lb = reinterpret_cast<int*>(lds + S_LB);
-  const int nt = (n + HT - 1) / HT;
   const long long r0 = (long long)row0 + (long long)blockIdx.x * HR;
-  const int t_lo = (int)blockIdx.y * ch, t_hi = min(((int)blockIdx.y + 1) * ch, nt);
+  const int t_lo = (int)blockIdx.y * ch, t_hi = min(((int)blockIdx.y + 1) * ch, pair_tile_count(n));
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int l16 = lane & 15, kg = lane >> 4;
   const int cbase = (int)blockIdx.z * NC + l16;  // this lane's column of result tile 0
-  const bool resident = hdb_rows_resident(Z, ld, d, n, r0, qs);
-  const int nch = (d + HD - 1) / HD;
+  const PairRows rows = pair_rows(Z, ld, d, n, r0, lds + PAIR_LDS_QS, lds + PAIR_LDS_CS);
   double4_t acc[NT];
 #pragma unroll
   for (int t = 0; t < NT; ++t) acc[t] = double4_t{0.0, 0.0, 0.0, 0.0};
   for (int ct = t_lo; ct < t_hi; ++ct) {
     const long long c0 = (long long)ct * HT;
     double s[HQ];
+    pair_tile(rows, c0, s);  // its first barrier also ends the previous tile's reads of kt and lb
 #pragma unroll
-    for (int q = 0; q < HQ; ++q) s[q] = 0.0;
-    // the first barrier in here also ends the previous tile's reads of kt and lb
-    for (int c = 0; c < nch; ++c) hdb_accumulate(hdb_stage(Z, ld, d, n, r0, c0, c, resident, qs, cs), cs, lane, wave, s);
-#pragma unroll
-    for (int q = 0; q < HQ; ++q) kt[(wave * HQ + q) * HR + lane] = c0 + wave * HQ + q < n ? sqrt(s[q]) : 0.0;
+    for (int q = 0; q < HQ; ++q) pair_kt_value(kt, lane, wave, q) = c0 + wave * HQ + q < n ? sqrt(s[q]) : 0.0;
     if (threadIdx.x < HT) lb[threadIdx.x] = c0 + threadIdx.x < n ? lab[c0 + threadIdx.x] : -1;
     __syncthreads();
-    // wave w: rows [16 w, 16 w + 16) of the tile x all NC columns.  Lane l holds A[row l & 15][k = l >> 4] and
-    // B[k = l >> 4][col l & 15] of each 16 x 16 x 4 step; step ks covers the tile's columns j = 4 ks + k.
+    // wave w: rows [16 w, 16 w + 16) of the tile x all NC columns (lane layouts: pair_tiles.h)
 #pragma unroll 2
     for (int ks = 0; ks < HT / 4; ++ks) {
       const int j = 4 * ks + kg;
-      const double a = kt[j * HR + 16 * wave + l16];
+      const double a = pair_kt_a(kt, j, wave, l16);
       const int rel = lb[j] - cbase;  // 16 t: row j of the tile is a member of this lane's column of result tile t
 #pragma unroll
       for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, rel == 16 * t ? 1.0 : 0.0, acc[t], 0, 0, 0);
     }
   }
-  // C/D of the f64 form: lane l, register r holds [row (l >> 4) + 4 r][col l & 15]
+  // acc[t][r] is [row (l >> 4) + 4 r][col l & 15] of result tile t
   double* out = part + ((long long)blockIdx.y * rpad + (long long)blockIdx.x * HR + 16 * wave + kg) * kpad + (int)blockIdx.z * NC + l16;
 #pragma unroll
   for (int t = 0; t < NT; ++t)
@@ -137,12 +123,7 @@ __global__ __launch_bounds__(256) void sil_finish_kernel(const double* __restric
 __global__ __launch_bounds__(256) void sil_mean_kernel(const double* __restrict__ v, long long n, double* __restrict__ out) {
   __shared__ double red[256];
   double sum = 0.0, comp = 0.0;
-  for (long long i = threadIdx.x; i < n; i += 256) {
-    const double x = v[i];
-    const double tsum = sum + x;
-    comp = comp + (fabs(sum) >= fabs(x) ? (sum - tsum) + x : (x - tsum) + sum);
-    sum = tsum;
-  }
+  for (long long i = threadIdx.x; i < n; i += 256) neumaier_add(sum, comp, v[i]);
   red[threadIdx.x] = sum + comp;
   __syncthreads();
   for (int o = 128; o > 0; o >>= 1) {
@@ -170,8 +151,6 @@ __global__ __launch_bounds__(256) void sil_medoid_row_kernel(const double* __res
 
 using namespace svae;
 
-#define ST(s) ((hipStream_t)(s))
-
 struct SilPlan {
   int nc, ch;
   unsigned gx, gy, gz;
@@ -184,8 +163,8 @@ static SilPlan sil_plan(int rows, int n, int K) {
   SilPlan p;
   p.nc = K <= 16 ? 16 : K <= 64 ? 64 : 256;
   p.gz = (unsigned)((K + p.nc - 1) / p.nc);
-  p.gx = (unsigned)(((long long)rows + HR - 1) / HR);
-  const int nt = (int)(((long long)n + HT - 1) / HT);
+  p.gx = (unsigned)pair_tile_count(rows);
+  const int nt = pair_tile_count(n);
   const long long xz = (long long)p.gx * p.gz;
   const int want = (int)std::min<long long>(std::min(nt, SIL_NGY), (SIL_BLOCKS + xz - 1) / xz);
   p.ch = (nt + want - 1) / want;
@@ -208,19 +187,14 @@ extern "C" long long svae_silhouette_work(int rows, int n, int K) {
 template <int NC>
 static int sil_launch_sums(const SilPlan& p, const double* Z, int ld, int d, int n, const int* lab, int row0, double* work, hipStream_t st) {
   static DeviceOnce once;
-  int dev;
-  if (once.need(&dev)) {
-    const hipError_t e = hipFuncSetAttribute((const void*)sil_sums_kernel<NC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SIL_LDS);
-    SVAE_REQUIRE(e == hipSuccess, SVAE_ERR_LAUNCH, "silhouette: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    once.done(dev);
-  }
+  if (int e = allow_lds(sil_sums_kernel<NC>, once, (int)SIL_LDS, "silhouette")) return e;
   hipLaunchKernelGGL(sil_sums_kernel<NC>, dim3(p.gx, p.gy, p.gz), dim3(256), SIL_LDS, st, Z, ld, d, n, lab, row0, p.ch, p.rpad, p.kpad, work);
   return check_launch("silhouette_sums");
 }
 
 extern "C" int svae_silhouette(const double* Z, int ld, int d, int n, const int* lab, const int* count, int K, int row0, int rows,
                                double* work, double* s, double* a, double* b, int* nearest, void* stream) {
-  SVAE_REQUIRE(Z && n >= 3 && n < (1 << 26) && d >= 1 && ld >= d, SVAE_ERR_ARG, "silhouette: bad rows (n=%d d=%d ld=%d)", n, d, ld);
+  if (int e = check_pair_rows("silhouette", Z, ld, d, n, 3, (1 << 26) - 1)) return e;
   SVAE_REQUIRE(K >= 2 && K <= SVAE_SIL_MAX_CLUSTERS && K <= n - 1, SVAE_ERR_ARG, "silhouette: bad cluster count (K=%d n=%d)", K, n);
   SVAE_REQUIRE(row0 >= 0 && rows >= 1 && rows <= n - row0, SVAE_ERR_ARG, "silhouette: bad row range (row0=%d rows=%d n=%d)", row0, rows, n);
   SVAE_REQUIRE(lab && count && work && s && a && b && nearest, SVAE_ERR_ARG, "silhouette: null argument");

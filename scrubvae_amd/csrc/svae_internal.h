@@ -1,6 +1,7 @@
 // Internal helpers shared by the HIP translation units of libscrubvae_hip.so.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <climits>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -43,6 +44,26 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
     }                                      \
   } while (0)
 
+#define ST(s) ((hipStream_t)(s))  // the C ABI's void* stream
+
+// Raise `kernel`'s dynamic LDS limit to `bytes`, once per device (one DeviceOnce per kernel, static at the call site)
+template <typename K>
+inline int allow_lds(K kernel, DeviceOnce& once, int bytes, const char* what) {
+  int dev;
+  if (once.need(&dev)) {
+    const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    SVAE_REQUIRE(e == hipSuccess, SVAE_ERR_LAUNCH, "%s: hipFuncSetAttribute: %s", what, hipGetErrorString(e));
+    once.done(dev);
+  }
+  return SVAE_OK;
+}
+
+// The row arguments of an all-pairs entry point (pair_tiles.h): n_min <= n <= n_max rows X [n][ld] of d features
+inline int check_pair_rows(const char* what, const double* X, int ld, int d, int n, int n_min, int n_max = INT_MAX) {
+  SVAE_REQUIRE(X && n >= n_min && n <= n_max && d >= 1 && ld >= d, SVAE_ERR_ARG, "%s: bad rows (n=%d d=%d ld=%d)", what, n, d, ld);
+  return SVAE_OK;
+}
+
 // ---- device helpers ---------------------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -61,6 +82,13 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
+}
+
+// One step of a compensated (Neumaier) sum; the total is sum + comp.  Additions only: nothing for the compiler to contract.
+__device__ __forceinline__ void neumaier_add(double& sum, double& comp, double v) {
+  const double tsum = sum + v;
+  comp = comp + (fabs(sum) >= fabs(v) ? (sum - tsum) + v : (v - tsum) + sum);
+  sum = tsum;
 }
 
 // block-wide sum for blockDim.x == 256 (4 waves); result valid in thread 0

@@ -37,6 +37,7 @@ import torch
 
 from .. import _lib, ops
 from .._lib import check
+from . import _device
 from .metrics import ConvergenceWarning as _MetricsConvergenceWarning
 
 _EPS10 = 10.0 * np.finfo(np.float64).eps
@@ -88,12 +89,7 @@ def _rows32(X):
     return a
 
 
-def _device_of(x):
-    if torch.is_tensor(x) and x.is_cuda:
-        return x.device
-    if not torch.cuda.is_available():
-        raise RuntimeError("GaussianMixture runs on the GPU (csrc/gmm.hip); no device is available")
-    return torch.device("cuda", torch.cuda.current_device())
+_device_of = functools.partial(_device._device_of, who="GaussianMixture runs on the GPU (csrc/gmm.hip); no device is available")
 
 
 def _host_log_det(P, diag):

@@ -27,6 +27,7 @@ whose sum is infinite) and the finite rows are clustered without them.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import numbers
 import time
 
@@ -35,6 +36,8 @@ import torch
 
 from .. import _lib, ops
 from .._lib import check
+from . import _device
+from ._device import _clock
 
 HIERARCHY_dtype = np.dtype([("left_node", np.intp), ("right_node", np.intp), ("value", np.float64), ("cluster_size", np.intp)])
 _OUTLIER_ENCODING = {"infinite": {"label": -2, "prob": 0.0}, "missing": {"label": -3, "prob": np.nan}}
@@ -71,17 +74,7 @@ def _rows(X):
     return t, int(sums.shape[0]), finite, infinite, missing
 
 
-def _device_of(x):
-    if torch.is_tensor(x) and x.is_cuda:
-        return x.device
-    if not torch.cuda.is_available():
-        raise RuntimeError("HDBSCAN runs on the GPU (csrc/hdbscan.hip); no device is available")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _sync(device):
-    torch.cuda.synchronize(device)
-    return time.perf_counter()
+_device_of = functools.partial(_device._device_of, who="HDBSCAN runs on the GPU (csrc/hdbscan.hip); no device is available")
 
 
 def mst_device(x, min_samples, alpha=1.0):
@@ -101,10 +94,10 @@ def _mst_on(x, min_samples, alpha, device):
     f64 = dict(dtype=torch.float64, device=device)
     i64 = dict(dtype=torch.int64, device=device)
     st = ops._stream()
-    t0 = _sync(device)
+    t0 = _clock(device)
     core = torch.empty(n, **f64)
     check(lib.svae_hdb_core(X.data_ptr(), d, d, n, int(min_samples), core.data_ptr(), st), "hdb_core")
-    t1 = _sync(device)
+    t1 = _clock(device)
     order = torch.sort(core, stable=True).indices
     Xs = X.index_select(0, order).contiguous()
     cs = core.index_select(0, order).contiguous()
@@ -127,7 +120,7 @@ def _mst_on(x, min_samples, alpha, device):
         check(lib.svae_hdb_relabel(comp_d.data_ptr(), n, map_d.data_ptr(), st), "hdb_relabel")
         n_comp = n_new.value
         rounds += 1
-    t2 = _sync(device)
+    t2 = _clock(device)
     if n_edges.value != n - 1:
         raise RuntimeError(f"hdb: {n_edges.value} MST edges for {n} rows")
     return core.cpu().numpy(), lo, hi, w, dict(core_s=t1 - t0, boruvka_s=t2 - t1, rounds=rounds)

@@ -56,8 +56,8 @@ Differences from the reference, by design:
 """
 from __future__ import annotations
 
+import functools
 import math
-import time
 import warnings
 
 import numpy as np
@@ -65,6 +65,8 @@ import torch
 
 from .. import _lib, ops
 from .._lib import check
+from . import _device
+from ._device import _clock
 
 _RTOL_PIVOT = 1e-12   # svae_spd_factor_solve_f64: pivots <= this x max diagonal are zero directions
 LOGREG_C, LOGREG_L1_RATIO = 1.0, 0.5
@@ -97,12 +99,7 @@ def kfold_assign(n, folds):
     return fold
 
 
-def _device_of(z):
-    if torch.is_tensor(z) and z.is_cuda:
-        return z.device
-    if not torch.cuda.is_available():
-        raise RuntimeError("the decodability metrics run on the GPU (csrc/decode.hip); no device is available")
-    return torch.device("cuda", torch.cuda.current_device())
+_device_of = functools.partial(_device._device_of, who="the decodability metrics run on the GPU (csrc/decode.hip); no device is available")
 
 
 def _rows(z, window, device):
@@ -713,11 +710,7 @@ def _mmd_device(X, Y, h, want_h, info=None, keep=None):
         st = ops._stream()
         hm = torch.full((2,), float("nan") if h is None else float(h), dtype=torch.float64, device=dev)  # med, h
 
-        def clock():
-            if info is not None:
-                torch.cuda.synchronize(dev)
-            return time.perf_counter()
-
+        clock = functools.partial(_clock, dev, info is not None)
         t0 = clock()
         if h is None:
             work = torch.empty(_lib.MMD_WORK_WORDS, dtype=torch.int64, device=dev)
@@ -837,11 +830,7 @@ def _mmd_null_device(Z, hm, nx, perms, info=None):
     work = torch.empty(lib.svae_mmd_null_blocks(n, min(P, _MMD_NULL_LAUNCH)), dtype=torch.float64, device=dev)
     pack_s = null_s = 0.0
 
-    def clock():
-        if info is not None:
-            torch.cuda.synchronize(dev)
-        return time.perf_counter()
-
+    clock = functools.partial(_clock, dev, info is not None)
     for p0 in range(0, P, _MMD_NULL_LAUNCH):
         count = min(_MMD_NULL_LAUNCH, P - p0)
         t0 = clock()

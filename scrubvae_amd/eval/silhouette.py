@@ -35,7 +35,6 @@ Differences from sklearn, by design:
 """
 from __future__ import annotations
 
-import time
 from collections import namedtuple
 
 import numpy as np
@@ -43,6 +42,7 @@ import torch
 
 from .. import _lib, ops
 from .._lib import check
+from ._device import _clock
 from .metrics import _device_of, _mmd_rows
 
 SIL_MAX_CLUSTERS = _lib.SIL_MAX_CLUSTERS  # the cap on the number of clusters
@@ -121,9 +121,7 @@ def _sil_device(x, lab, count, info=None):
         work = torch.empty(words, dtype=torch.float64, device=dev)
         s, a, b = (torch.empty(m, dtype=torch.float64, device=dev) for _ in range(3))
         nearest = torch.empty(m, dtype=torch.int32, device=dev)
-        if info is not None:
-            torch.cuda.synchronize(dev)
-        t0 = time.perf_counter()
+        t0 = _clock(dev, info is not None)
         ranges = 0
         for row0 in range(0, m, _SIL_ROWS_PER_LAUNCH):
             rows = min(_SIL_ROWS_PER_LAUNCH, m - row0)
@@ -133,8 +131,7 @@ def _sil_device(x, lab, count, info=None):
                                       s[row0:].data_ptr(), a[row0:].data_ptr(), b[row0:].data_ptr(), nearest[row0:].data_ptr(), st),
                   "silhouette")
         if info is not None:
-            torch.cuda.synchronize(dev)
-            info.update(sil_s=time.perf_counter() - t0)
+            info.update(sil_s=_clock(dev) - t0)
         _SIL_LAST.update(work=words, ranges=ranges)
     return s, a, b, nearest, labd
 
