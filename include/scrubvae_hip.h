@@ -704,6 +704,23 @@ int svae_silhouette_mean(const double* v, long long n, double* out, void* stream
 /* row[c] = the lowest row i of cluster c with the smallest a[i] (a [n] >= 0, finite): the medoid.  key [K] device scratch. */
 int svae_silhouette_medoids(const double* a, const int* lab, int n, int K, unsigned long long* key, long long* row, void* stream);
 
+/* ------------------------------------------------------- Exact k nearest neighbours of every latent (csrc/knn.hip) --------- */
+/* Z [n][ld] fp64 rows, not centred, d >= 1, 2 <= n < 2^31, 1 <= k <= min(n - 1, SVAE_KNN_MAX_K).  The neighbours of row i are the
+ * k smallest keys (s_ij, j) over j != i, compared strictly and lexicographically: s_ij the squared distance of csrc/pair_tiles.h
+ * (feature order, no FMA) compared by its uint64 bit pattern, then the lower j.  The row itself is left out by index, not by
+ * distance: a duplicate of row i is a neighbour at distance 0.  idx [n][k] and dist [n][k] hold the neighbours of row i in
+ * ascending key order, dist = the correctly rounded sqrt(s).  group [n] (nullable) keeps only the candidates j with
+ * group[j] != group[i]; the caller guarantees that every row keeps at least k candidates (with fewer, the tail of that row's
+ * idx and dist is left unwritten).  One pass over the n^2 distances: a block keeps the running best k of its 64 rows in LDS;
+ * nothing of size n^2 or n (n / 64) is stored.  The result is unique, so bit-reproducible, and does not depend on the column
+ * chunks.  SVAE_KNN_MAX_K is what 160 KiB of LDS hold next to the staged rows: 64 rows x 154 buffered candidates, of which a
+ * tile of 64 columns may add 64 to a row (90 = 3 x 30: what t-SNE asks for at perplexity 30). */
+#define SVAE_KNN_MAX_K 90
+/* bytes of work that svae_knn needs (0 for n < 2, k < 1, k > n - 1 or k > SVAE_KNN_MAX_K): column chunks (at most 8, 1 once
+ * the grid holds 512 blocks) x rows padded to 64 x k x 12 (a uint64 key and an int32 index per kept candidate) */
+long long svae_knn_work(int n, int k);
+int svae_knn(const double* Z, int ld, int d, int n, int k, const int* group, void* work, int* idx, double* dist, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -203,6 +203,8 @@ SIGNATURES = {
     "svae_silhouette": (I, [P, I, I, I, P, P, I, I, I, P, P, P, P, P, P]),
     "svae_silhouette_mean": (I, [P, LL, P, P]),
     "svae_silhouette_medoids": (I, [P, P, I, I, P, P, P]),
+    "svae_knn_work": (LL, [I, I]),
+    "svae_knn": (I, [P, I, I, I, I, P, P, P, P, P]),
 }
 
 _lib = None
@@ -239,6 +241,7 @@ GMM_MAX_COMPONENTS, GMM_MAX_TRIALS = 64, 8  # include/scrubvae_hip.h SVAE_GMM_*
 MMD_WORK_WORDS = 8256  # include/scrubvae_hip.h SVAE_MMD_WORK_WORDS
 MMD_NULL_MAX = 65536  # include/scrubvae_hip.h SVAE_MMD_NULL_MAX
 SIL_MAX_CLUSTERS = 4096  # include/scrubvae_hip.h SVAE_SIL_MAX_CLUSTERS
+KNN_MAX_K = 90  # include/scrubvae_hip.h SVAE_KNN_MAX_K
 MAX_LOSS_TERMS = 48  # include/scrubvae_hip.h SVAE_MAX_LOSS_TERMS
 ERR_SHAPE, ERR_ALIGN, ERR_WORKSPACE, ERR_LAUNCH, ERR_ARG = -1, -2, -3, -4, -5  # include/scrubvae_hip.h svae_status
 

@@ -1,6 +1,8 @@
 from .cluster import GaussianMixture, dbscan, gmm  # noqa: F401
 from .eval import generative_restrictiveness  # noqa: F401
 from .hdbscan import HDBSCAN  # noqa: F401
-from .metrics import (cluster_entropy, hungarian_match, lda_rand_cv, linear_rand_cv, log_class_rand_cv, mlp_rand_cv,  # noqa: F401
-                      mmd_bandwidth, mmd_estimate, mmd_permutation_test, mmd_permutations, qda_rand_cv, shannon_entropy)
+from .metrics import (cluster_entropy, hungarian_match, knn_class_rand_cv, knn_reg_rand_cv, lda_rand_cv, linear_rand_cv,  # noqa: F401
+                      log_class_rand_cv, mlp_rand_cv, mmd_bandwidth, mmd_estimate, mmd_permutation_test, mmd_permutations,
+                      qda_rand_cv, shannon_entropy)
+from .neighbors import kneighbors, kneighbors_graph, knn_label_purity  # noqa: F401
 from .silhouette import cluster_medoids, cluster_silhouette, silhouette_samples, silhouette_score  # noqa: F401

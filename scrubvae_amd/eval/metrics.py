@@ -7,6 +7,8 @@ variable from the latents, on the device.
     qda_rand_cv(z, y_true, window=51, folds=5)        accuracy of QuadraticDiscriminantAnalysis()
 
     lda_rand_cv(z, y_true, window=51, folds=5)        accuracy of LinearDiscriminantAnalysis()
+    knn_class_rand_cv(z, y_true, window=51, folds=5, n_neighbors=5)   accuracy of KNeighborsClassifier(n_neighbors)
+    knn_reg_rand_cv(z, y_true, window=51, folds=5, n_neighbors=5)     R^2 of KNeighborsRegressor(n_neighbors)
 
 Each returns a list of `folds` floats in fold order, as the reference's `rand_cv` wrapper does: rows z[0::window], then
 KFold(n_splits=folds, shuffle=True, random_state=100), restated here in numpy (this module does not import sklearn).  After the
@@ -26,6 +28,9 @@ Differences from the reference, by design:
     there is never predicted in that fold.
   - lda_rand_cv raises the ValueErrors of qda_rand_cv, also for a class with a single training row (sklearn's LDA accepts one).
 Limits (ValueError): z_dim <= 128, <= 8 regression targets, <= 64 classes, <= 10 folds.
+The two kNN probes are non-parametric: the rows go to fp64 and one exact neighbour search (csrc/knn.hip, eval/neighbors.py) with
+group = fold gives every row its n_neighbors nearest training rows of its fold; uniform weights, a tied vote goes to the lowest
+class, the regression mean is summed in neighbour order.  Their limits are those of kneighbors, not the ones above.
 
 The rest of the reference's eval/metrics.py:
 
@@ -360,6 +365,81 @@ def lda_rand_cv(z, y_true, window=51, folds=5):
     """Accuracy per fold of LinearDiscriminantAnalysis() (reference metrics.py:293-298): the class means and one pooled covariance
     per training fold (within-class scatter over n_train - classes), priors = the class frequencies."""
     return _lda(z, y_true, window, folds)
+
+
+def _knn_cv_check(z, window, folds, n_neighbors):
+    """the argument errors of the kNN probes -> (the rows z[0::window] in fp64, their folds, k, the folds as int32 groups)"""
+    from .neighbors import _knn_check
+    t = (z if torch.is_tensor(z) else np.asarray(z))[0::window]
+    if t.ndim != 2:
+        t = t.reshape(t.shape[0], -1)
+    fold = kfold_assign(t.shape[0], folds)
+    x, k, grp = _knn_check(t, n_neighbors, fold)
+    return x, fold, k, grp
+
+
+def _knn_cv_search(x, k, grp):
+    """each row's k nearest rows of the other folds, int64 [n, k] on the device: ONE neighbour search with group = fold"""
+    from .neighbors import _knn_device
+    return _knn_device(x, k, grp)[1].long()
+
+
+def _knn_class(z, y_true, window, folds, n_neighbors, want_rows=False):
+    x, fold, k, grp = _knn_cv_check(z, window, folds, n_neighbors)
+    n = x.shape[0]
+    classes, cls = _labels(y_true, window)
+    if len(cls) != n:
+        raise ValueError(f"y_true gives {len(cls)} rows after the downsample, z gives {n}")
+    K = len(classes)
+    idx = _knn_cv_search(x, k, grp)
+    cls_d = torch.from_numpy(cls).to(idx.device)
+    votes = torch.zeros(n, K, dtype=torch.int64, device=idx.device)
+    votes.scatter_add_(1, cls_d[idx], torch.ones_like(idx))
+    # one integer key per (votes, class): its maximum is unique, the most votes and then the lowest class
+    pred = (votes * K + (K - 1 - torch.arange(K, device=idx.device))[None, :]).argmax(1).cpu().numpy()
+    hit = pred == cls
+    acc = [float(hit[fold == f].sum()) / float((fold == f).sum()) for f in range(int(folds))]
+    return dict(acc=acc, fold=fold, pred=classes[pred]) if want_rows else acc
+
+
+def knn_class_rand_cv(z, y_true, window=51, folds=5, n_neighbors=5):
+    """Accuracy per fold of KNeighborsClassifier(n_neighbors) with uniform weights, fitted on the other folds: the majority vote
+    of the row's n_neighbors nearest training rows, a tied vote to the lowest class in np.unique order (sklearn's rule)."""
+    return _knn_class(z, y_true, window, folds, n_neighbors)
+
+
+def _knn_r2(y, pred):
+    """sklearn's r2_score(y, pred) for [m, outputs] fp64 arrays: 1 - SS_res / SS_tot per output (for a constant target 1 where
+    the fit is exact, else 0), averaged uniformly"""
+    ss_res = ((y - pred) ** 2).sum(0)
+    ss_tot = ((y - y.mean(0)) ** 2).sum(0)
+    r2 = np.where(ss_tot != 0, 1.0 - ss_res / np.where(ss_tot != 0, ss_tot, 1.0), np.where(ss_res == 0, 1.0, 0.0))
+    return float(r2.mean())
+
+
+def _knn_reg(z, y_true, window, folds, n_neighbors, want_rows=False):
+    x, fold, k, grp = _knn_cv_check(z, window, folds, n_neighbors)
+    n = x.shape[0]
+    y = _host(y_true, window).astype(np.float64)
+    y = y.reshape(y.shape[0], -1)
+    if y.shape[0] != n:
+        raise ValueError(f"y_true gives {y.shape[0]} rows after the downsample, z gives {n}")
+    if not np.isfinite(y).all():
+        raise ValueError("y_true holds non-finite values")
+    idx = _knn_cv_search(x, k, grp)
+    yd = torch.from_numpy(np.ascontiguousarray(y)).to(idx.device)
+    acc = yd[idx[:, 0]]
+    for t in range(1, k):  # in neighbour order, every addition rounded on its own
+        acc = acc + yd[idx[:, t]]
+    pred = acc.cpu().numpy() / k  # on the host: the device's division by a scalar multiplies by its rounded reciprocal
+    r2 = [_knn_r2(y[fold == f], pred[fold == f]) for f in range(int(folds))]
+    return dict(r2=r2, fold=fold, pred=pred) if want_rows else r2
+
+
+def knn_reg_rand_cv(z, y_true, window=51, folds=5, n_neighbors=5):
+    """R^2 per fold of KNeighborsRegressor(n_neighbors) fitted on the other folds: the fp64 mean of the targets of the row's
+    n_neighbors nearest training rows, summed in neighbour order; r2_score's uniform average over the outputs."""
+    return _knn_reg(z, y_true, window, folds, n_neighbors)
 
 
 def logreg_problems(cnt_fc):

@@ -1,0 +1,124 @@
+"""Exact k nearest neighbours of every latent, on the device (csrc/knn.hip).
+
+    kneighbors(z, n_neighbors, *, group=None, return_distance=True)    (dist [n, k] float64, idx [n, k] int64) numpy, or idx alone
+    kneighbors_graph(z, n_neighbors, mode="connectivity")              scipy.sparse.csr_matrix [n, n]; mode="distance": the distances
+    knn_label_purity(z, labels, n_neighbors)                           (share of the k neighbours with the row's own label [n], its mean)
+
+z is [n, d], numpy or torch, host or device, any float dtype; the rows go to fp64 uncentred, as for mmd_* and the silhouette.
+
+The neighbours of row i are the k smallest keys (s_ij, j) over j != i: s_ij the squared distance in the arithmetic of
+csrc/pair_tiles.h (feature order, every operation rounded on its own: sklearn's KD-tree metric), then the lower index.  The row
+itself is left out by index, not by distance, so a duplicate of row i is a neighbour at distance 0, and exact ties come out in
+index order.  Row i of the result holds its neighbours in ascending key order with dist = sqrt(s).  This is
+sklearn.neighbors.NearestNeighbors(n_neighbors).fit(z).kneighbors() (the query point excluded), with the ties decided.  The key is
+strict, so the result is unique: bit-reproducible, and independent of how the device splits the work.
+
+group [n] (integers) keeps for row i only the candidates j with group[j] != group[i]: with group = the cross-validation fold, one
+call gives every row's neighbours among the training rows of its fold (eval.metrics.knn_class_rand_cv / knn_reg_rand_cv).
+
+One pass over the n^2 distances, nothing of size n^2 stored; n_neighbors <= KNN_MAX_K = 90 (what the kernel's LDS holds).
+ValueError for non-finite rows and for every argument out of range, before any device work."""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from .. import _lib, ops
+from .._lib import check
+from ._device import _clock
+from .metrics import _device_of, _mmd_rows
+from .silhouette import _sil_labels
+
+KNN_MAX_K = _lib.KNN_MAX_K             # the cap on n_neighbors
+_KNN_CALLS = {"knn": 0}                # launches of svae_knn by this process
+_KNN_LAST = {"work": 0, "chunks": 0}   # bytes of work and column chunks per row tile of the last run
+
+
+def _knn_check(z, n_neighbors, group=None):
+    """the argument errors, before any device work -> (fp64 rows, k, group int32 [n] numpy or None)"""
+    x = _mmd_rows(z, "z")
+    n, d = x.shape
+    if d < 1:
+        raise ValueError("z must have at least one feature")
+    if isinstance(n_neighbors, bool) or not isinstance(n_neighbors, (int, np.integer)):
+        raise ValueError(f"n_neighbors must be an integer, got {n_neighbors!r}")
+    k = int(n_neighbors)
+    if k < 1:
+        raise ValueError(f"Expected n_neighbors > 0. Got {k}")
+    if k > n - 1:
+        raise ValueError(f"Expected n_neighbors <= n_samples - 1 (the row itself is not a neighbour), but n_neighbors = {k}, n_samples = {n}")
+    if k > KNN_MAX_K:
+        raise ValueError(f"at most {KNN_MAX_K} neighbours are supported, got {k}")
+    if n >= 2 ** 31:
+        raise ValueError(f"at most 2^31 - 1 rows are supported, got {n}")
+    grp = None
+    if group is not None:
+        _, grp, count = np.unique(_sil_labels(group, n), return_inverse=True, return_counts=True)
+        grp = grp.reshape(-1).astype(np.int32)
+        if n - count.max() < k:
+            raise ValueError(f"group {int(count.argmax())} (in np.unique order) holds {int(count.max())} of the {n} rows: its rows keep "
+                             f"fewer than n_neighbors = {k} candidates")
+    return x, k, grp
+
+
+def _knn_device(x, k, grp, info=None):
+    """(dist fp64 [n, k], idx int32 [n, k]) on the device of x (or the current one).  info (a dict) receives the synchronised
+    host-clock time knn_s of the svae_knn call."""
+    dev = _device_of(x)
+    n, d = x.shape
+    with torch.cuda.device(dev):
+        lib = _lib.lib()
+        if not torch.is_tensor(x):
+            x = torch.from_numpy(x if x.flags.writeable else x.copy())  # torch refuses to share a read-only array
+        Z = x.to(dev).contiguous()
+        gd = None if grp is None else torch.from_numpy(grp).to(dev)
+        nbytes = lib.svae_knn_work(n, k)
+        work = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+        idx = torch.empty(n, k, dtype=torch.int32, device=dev)
+        dist = torch.empty(n, k, dtype=torch.float64, device=dev)
+        t0 = _clock(dev, info is not None)
+        _KNN_CALLS["knn"] += 1
+        check(lib.svae_knn(Z.data_ptr(), d, d, n, k, ops._p(gd), work.data_ptr(), idx.data_ptr(), dist.data_ptr(), ops._stream()), "knn")
+        if info is not None:
+            info.update(knn_s=_clock(dev) - t0)
+        _KNN_LAST.update(work=nbytes, chunks=nbytes // (-(-n // 64) * 64 * k * 12))
+    return dist, idx
+
+
+def kneighbors(z, n_neighbors, *, group=None, return_distance=True):
+    """The n_neighbors nearest other rows of every row of z: (dist [n, k] float64, idx [n, k] int64) as numpy arrays, or idx alone
+    (sklearn's NearestNeighbors(n_neighbors).fit(z).kneighbors()).  group [n]: only rows of another group are candidates."""
+    x, k, grp = _knn_check(z, n_neighbors, group)
+    dist, idx = _knn_device(x, k, grp)
+    idx = idx.cpu().numpy().astype(np.int64)
+    return (dist.cpu().numpy(), idx) if return_distance else idx
+
+
+def _graph(dist, idx, n, mode):
+    """host glue: the csr_matrix [n, n] of idx [n, k] with 1.0 or dist [n, k] as data, each row in neighbour order"""
+    from scipy.sparse import csr_matrix
+    k = idx.shape[1]
+    data = np.ones(n * k) if mode == "connectivity" else np.ascontiguousarray(dist, dtype=np.float64).reshape(-1)
+    return csr_matrix((data, np.ascontiguousarray(idx).reshape(-1), np.arange(0, n * k + 1, k)), shape=(n, n))
+
+
+def kneighbors_graph(z, n_neighbors, mode="connectivity"):
+    """The k-neighbour graph as a scipy.sparse.csr_matrix [n, n] (sklearn.neighbors.kneighbors_graph, include_self=False): row i
+    holds its neighbours in key order, with 1.0 (mode="connectivity") or the distance (mode="distance")."""
+    if mode not in ("connectivity", "distance"):
+        raise ValueError(f'Unsupported mode, must be one of "connectivity", or "distance" but got "{mode}" instead')
+    x, k, _ = _knn_check(z, n_neighbors)
+    dist, idx = _knn_device(x, k, None)
+    return _graph(dist.cpu().numpy(), idx.cpu().numpy().astype(np.int64), x.shape[0], mode)
+
+
+def knn_label_purity(z, labels, n_neighbors):
+    """(the share of each row's n_neighbors neighbours that carry the row's own label [n] float64, its mean as a float): do the
+    windows of one animal or class still sit next to each other?  labels [n], any integer dtype, numpy or torch."""
+    x, k, _ = _knn_check(z, n_neighbors)
+    _, lab = np.unique(_sil_labels(labels, x.shape[0]), return_inverse=True)
+    _, idx = _knn_device(x, k, None)
+    labd = torch.from_numpy(lab.reshape(-1).astype(np.int64)).to(idx.device)
+    same = (labd[idx.long()] == labd[:, None]).sum(1)
+    share = same.cpu().numpy().astype(np.float64) / k
+    return share, float(share.mean())
