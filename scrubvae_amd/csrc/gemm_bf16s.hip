@@ -913,156 +913,61 @@ static void launch_split_ws(const SplitGatherArgs& sa, dim3 grid, hipStream_t st
   else hipLaunchKernelGGL((gather_gemm_bf16s_ws_kernel<BM, BN, 1, CWR, CWC, D>), grid, block, 0, st, sa);
 }
 
-#ifdef SVAE_ABLATION_KERNELS  // timing experiments with parts of the work removed (wrong results): python scrubvae_amd/build.py --ablation
-static void launch_split_dbg(const SplitGatherArgs& sa, dim3 grid, hipStream_t st, int dbg) {
-  const dim3 block(64 * 12);
-#define SVAE_DBG_CASE(N) case N: hipLaunchKernelGGL((gather_gemm_bf16s_ws_kernel<128, 128, 3, 4, 2, 2, N>), grid, block, 0, st, sa); break;
-  switch (dbg) {
-    SVAE_DBG_CASE(0) SVAE_DBG_CASE(1) SVAE_DBG_CASE(2) SVAE_DBG_CASE(3) SVAE_DBG_CASE(4) SVAE_DBG_CASE(8) SVAE_DBG_CASE(12)
-    SVAE_DBG_CASE(5) SVAE_DBG_CASE(13) SVAE_DBG_CASE(15) SVAE_DBG_CASE(7)
-    default: break;
+// The 8-wave halo kernel (V = 8 / 9 / 19 / 29): the instance for (pieces, fp16, image rows, up2).  The corners that are not built
+// -- split_gather_geometry refuses them -- stay uninstantiated: false.
+template <int BM, int BN, int WR, int WC, int P, bool H>
+static bool launch_halo_rows(const SplitGatherArgs& sa, const SplitGeo& geo, dim3 grid, hipStream_t st) {
+  constexpr int R0 = BM == 128 ? 160 : 320, R1 = BM == 128 ? 264 : 528;
+  constexpr bool HAS_R1 = BN != 256 && !(BM == 256 && P == 3 && BN > 64);  // 256 x 256: <= 320 rows; 3 pieces of 528 rows: 64 columns
+  constexpr bool HAS_UP = BN != 160, HAS_UP_R1 = HAS_R1 && BM == 128;        // up2 on 256-row tiles: 320-row images
+#define SVAE_HALO(R_, UP_) \
+  do { hipLaunchKernelGGL((gather_halo_bf16s_kernel<BM, BN, P, WR, WC, R_, H, UP_>), grid, dim3(512), 0, st, sa); return true; } while (0)
+  if (geo.rmax == R0) {
+    if (!sa.g.up) SVAE_HALO(R0, false);
+    if constexpr (HAS_UP) SVAE_HALO(R0, true);
+  } else if constexpr (HAS_R1) {
+    if (!sa.g.up) SVAE_HALO(R1, false);
+    if constexpr (HAS_UP_R1) SVAE_HALO(R1, true);
   }
-#undef SVAE_DBG_CASE
-}
-#endif
-
-template <int BN>
-static int launch_halo(const SplitGatherArgs& sa, dim3 grid, hipStream_t st, int pieces, int rows) {
-  if (pieces != 3 && pieces != 2 && pieces != SVAE_PIECES_F16X2) { set_error("split gather: the halo kernel is built for 2 or 3 pieces"); return SVAE_ERR_SHAPE; }
-  if (rows > 264) { set_error("split gather: halo image of %d rows does not fit", rows); return SVAE_ERR_SHAPE; }
-  if (sa.g.up) {  // fused x2 upsample of the gathered operand
-#define SVAE_HUP(P_, H_) do { if (rows <= 160) hipLaunchKernelGGL((gather_halo_bf16s_kernel<128, BN, P_, 4, 2, 160, H_, true>), grid, dim3(512), 0, st, sa); \
-                              else hipLaunchKernelGGL((gather_halo_bf16s_kernel<128, BN, P_, 4, 2, 264, H_, true>), grid, dim3(512), 0, st, sa); } while (0)
-    if (pieces == SVAE_PIECES_F16X2) SVAE_HUP(2, true); else if (pieces == 3) SVAE_HUP(3, false); else SVAE_HUP(2, false);
-#undef SVAE_HUP
-    return SVAE_OK;
-  }
-  if (pieces == SVAE_PIECES_F16X2) {
-    if (rows <= 160) hipLaunchKernelGGL((gather_halo_bf16s_kernel<128, BN, 2, 4, 2, 160, true>), grid, dim3(512), 0, st, sa);
-    else hipLaunchKernelGGL((gather_halo_bf16s_kernel<128, BN, 2, 4, 2, 264, true>), grid, dim3(512), 0, st, sa);
-  } else if (pieces == 3) {
-    if (rows <= 160) hipLaunchKernelGGL((gather_halo_bf16s_kernel<128, BN, 3, 4, 2, 160>), grid, dim3(512), 0, st, sa);
-    else hipLaunchKernelGGL((gather_halo_bf16s_kernel<128, BN, 3, 4, 2, 264>), grid, dim3(512), 0, st, sa);
-  } else {
-    if (rows <= 160) hipLaunchKernelGGL((gather_halo_bf16s_kernel<128, BN, 2, 4, 2, 160>), grid, dim3(512), 0, st, sa);
-    else hipLaunchKernelGGL((gather_halo_bf16s_kernel<128, BN, 2, 4, 2, 264>), grid, dim3(512), 0, st, sa);
-  }
-  return SVAE_OK;
+#undef SVAE_HALO
+  return false;
 }
 
-// V = 9: the halo kernel on 256-row tiles (code 9128NNN; 8 waves of 64 x 64): half the weight-piece bytes per FLOP through
-// the vector-memory path; pays once the problem has >= 2 x 256 such row tiles (batch >= 2048 for the deep layers)
-template <int BN>
-static int launch_halo256(const SplitGatherArgs& sa, dim3 grid, hipStream_t st, int pieces, int rows) {
-  if (pieces != 3 && pieces != 2 && pieces != SVAE_PIECES_F16X2) { set_error("split gather: the halo kernel is built for 2 or 3 pieces"); return SVAE_ERR_SHAPE; }
-  if (rows > 528 || (pieces == 3 && rows > 320 && BN > 64)) { set_error("split gather: 256-row halo image of %d rows does not fit", rows); return SVAE_ERR_SHAPE; }
-  if (sa.g.up) {  // fused x2 upsample of the gathered operand (images of up to 320 rows: 6-tap convs on 256-row tiles need 298)
-    if (rows > 320) { set_error("split gather: the fused upsample exists for 256-row halo images of <= 320 rows (%d)", rows); return SVAE_ERR_SHAPE; }
-    if (pieces == SVAE_PIECES_F16X2) hipLaunchKernelGGL((gather_halo_bf16s_kernel<256, BN, 2, 4, 2, 320, true, true>), grid, dim3(512), 0, st, sa);
-    else if (pieces == 3) hipLaunchKernelGGL((gather_halo_bf16s_kernel<256, BN, 3, 4, 2, 320, false, true>), grid, dim3(512), 0, st, sa);
-    else hipLaunchKernelGGL((gather_halo_bf16s_kernel<256, BN, 2, 4, 2, 320, false, true>), grid, dim3(512), 0, st, sa);
-    return SVAE_OK;
+template <int BM, int BN, int WR, int WC>
+static bool launch_halo(const SplitGatherArgs& sa, const SplitGeo& geo, dim3 grid, hipStream_t st, int pieces) {
+  if (pieces == SVAE_PIECES_F16X2) return launch_halo_rows<BM, BN, WR, WC, 2, true>(sa, geo, grid, st);
+  if (pieces == 2) return launch_halo_rows<BM, BN, WR, WC, 2, false>(sa, geo, grid, st);
+  if constexpr (BN <= 128) {  // the 256 x 160 and 256 x 256 tiles: 2 pieces
+    if (pieces == 3) return launch_halo_rows<BM, BN, WR, WC, 3, false>(sa, geo, grid, st);
   }
-  if (pieces == SVAE_PIECES_F16X2) {
-    if (rows <= 320) hipLaunchKernelGGL((gather_halo_bf16s_kernel<256, BN, 2, 4, 2, 320, true>), grid, dim3(512), 0, st, sa);
-    else hipLaunchKernelGGL((gather_halo_bf16s_kernel<256, BN, 2, 4, 2, 528, true>), grid, dim3(512), 0, st, sa);
-  } else if (pieces == 3) {
-    if (rows <= 320) hipLaunchKernelGGL((gather_halo_bf16s_kernel<256, BN, 3, 4, 2, 320>), grid, dim3(512), 0, st, sa);
-    else hipLaunchKernelGGL((gather_halo_bf16s_kernel<256, 64, 3, 4, 2, 528>), grid, dim3(512), 0, st, sa);
-  } else {
-    if (rows <= 320) hipLaunchKernelGGL((gather_halo_bf16s_kernel<256, BN, 2, 4, 2, 320>), grid, dim3(512), 0, st, sa);
-    else hipLaunchKernelGGL((gather_halo_bf16s_kernel<256, BN, 2, 4, 2, 528>), grid, dim3(512), 0, st, sa);
-  }
-  return SVAE_OK;
+  return false;
 }
 
-// V = 29: the halo kernel on 256 x 256 tiles, 4 x 2 waves of 64 x 128 (code 29128128; the fields of the code are placeholders): a
-// quarter fewer operand bytes per multiply through the CU's fetch path than 256 x 128.  Two pieces, images of <= 320 rows.
-static int launch_halo256x256(const SplitGatherArgs& sa, dim3 grid, hipStream_t st, int pieces, int rows) {
-  if (pieces != 2 && pieces != SVAE_PIECES_F16X2) { set_error("split gather: the 256 x 256 halo tile is built for 2 pieces"); return SVAE_ERR_SHAPE; }
-  if (rows > 320) { set_error("split gather: 256 x 256 halo tile: image of %d rows does not fit", rows); return SVAE_ERR_SHAPE; }
-  if (sa.g.up) {  // fused x2 upsample of the gathered operand
-    if (pieces == SVAE_PIECES_F16X2) hipLaunchKernelGGL((gather_halo_bf16s_kernel<256, 256, 2, 4, 2, 320, true, true>), grid, dim3(512), 0, st, sa);
-    else hipLaunchKernelGGL((gather_halo_bf16s_kernel<256, 256, 2, 4, 2, 320, false, true>), grid, dim3(512), 0, st, sa);
-    return SVAE_OK;
-  }
-  if (pieces == SVAE_PIECES_F16X2) hipLaunchKernelGGL((gather_halo_bf16s_kernel<256, 256, 2, 4, 2, 320, true>), grid, dim3(512), 0, st, sa);
-  else hipLaunchKernelGGL((gather_halo_bf16s_kernel<256, 256, 2, 4, 2, 320>), grid, dim3(512), 0, st, sa);
-  return SVAE_OK;
-}
-
-// V = 19: the halo kernel on 256 x 160 tiles, 8 x 1 waves of 32 x 160 (code 19128128; the fields of the code are placeholders).  For
-// the output conv (141 -> 144 channels): ONE column tile instead of three 64-wide ones -- 10 % instead of 25 % of the matrix work on
-// padding columns, and the activation image of a channel block staged once instead of three times.  Two pieces (bf16 or fp16).
-static int launch_halo256_wide(const SplitGatherArgs& sa, dim3 grid, hipStream_t st, int pieces, int rows) {
-  if (pieces != 2 && pieces != SVAE_PIECES_F16X2) { set_error("split gather: the 256 x 160 halo tile is built for 2 pieces"); return SVAE_ERR_SHAPE; }
-  if (rows > 528) { set_error("split gather: 256-row halo image of %d rows does not fit", rows); return SVAE_ERR_SHAPE; }
-  if (pieces == SVAE_PIECES_F16X2) {
-    if (rows <= 320) hipLaunchKernelGGL((gather_halo_bf16s_kernel<256, 160, 2, 8, 1, 320, true>), grid, dim3(512), 0, st, sa);
-    else hipLaunchKernelGGL((gather_halo_bf16s_kernel<256, 160, 2, 8, 1, 528, true>), grid, dim3(512), 0, st, sa);
-  } else {
-    if (rows <= 320) hipLaunchKernelGGL((gather_halo_bf16s_kernel<256, 160, 2, 8, 1, 320>), grid, dim3(512), 0, st, sa);
-    else hipLaunchKernelGGL((gather_halo_bf16s_kernel<256, 160, 2, 8, 1, 528>), grid, dim3(512), 0, st, sa);
-  }
-  return SVAE_OK;
-}
-
-// tile code V*1000000 + BM*1000 + BN.  V = 0: 4 waves, double-buffered LDS;  1: 4 waves, single LDS buffer;
-// 2: 8 waves (4x2), single buffer;  3: 8 waves, double-buffered (BM = 128 only);
-// 4: wave-specialised, 4 producer + 8 consumer waves, 2 tiles in flight;  5: same with 4 consumers;
-// 6 / 7: as 4 / 5 with 3 tiles in flight;  8: halo image kernel (BM = 128, 8 waves)
+// what the code means and whether it exists: split_gather_geometry (split_gather.h, with the list of the variants); here only
+// the template instance is picked
 static int launch_split_gather(SplitGatherArgs& sa, hipStream_t st, int code, int pieces) {
   GatherArgs& g = sa.g;
-  Tile t;
-  if (!decode_tile(code, t)) { t = pick_tile(g.M[0], g.M[1], g.N); t.dma = 1; if (g.up) { t.bm = 128; t.dma = 8; } }
-  const int v = t.dma;
-  if (g.up && v != 8 && v != 9 && v != 29) {
-    set_error("split gather: the fused x2 upsample of the input exists in the halo kernels (tile codes 8 / 9 / 29), not in code %d", code);
-    return SVAE_ERR_SHAPE;
-  }
-  if (v >= 10 && v != 19 && v != 29) {
-    bool handled = false;
-    const int e = launch_split_halo_ws(sa, st, t, code, pieces, &handled);
-    if (handled) return e;
-  }
-  if (v == 29) {  // 256 x 256 tiles
-    if (t.bm != 128 || t.bn != 128) { set_error("split gather: tile code %d unsupported", code); return SVAE_ERR_SHAPE; }
-    for (int p = 0; p < 2; ++p) g.blocks_m[p] = (int)((g.M[p] + 255) / 256);
-    const int nb = g.blocks_m[0] + g.blocks_m[1];
-    if (nb == 0) return SVAE_OK;
-    if (int e = launch_halo256x256(sa, dim3(nb, (g.N + 255) / 256), st, pieces, halo_rows(g, 256))) return e;
-    return check_launch("gather_halo_bf16s<256,256>");
-  }
-  if (v == 19) {  // 256 x 160 tiles
-    if (t.bm != 128 || t.bn != 128) { set_error("split gather: tile code %d unsupported", code); return SVAE_ERR_SHAPE; }
-    for (int p = 0; p < 2; ++p) g.blocks_m[p] = (int)((g.M[p] + 255) / 256);
-    const int nb = g.blocks_m[0] + g.blocks_m[1];
-    if (nb == 0) return SVAE_OK;
-    if (int e = launch_halo256_wide(sa, dim3(nb, (g.N + 159) / 160), st, pieces, halo_rows(g, 256))) return e;
-    return check_launch("gather_halo_bf16s<256,160>");
-  }
-  if (v == 9) {  // 256-row halo tiles, encoded with a 128 row field
-    if (t.bm != 128) { set_error("split gather: tile code %d unsupported", code); return SVAE_ERR_SHAPE; }
-    for (int p = 0; p < 2; ++p) g.blocks_m[p] = (int)((g.M[p] + 255) / 256);
-    const int nb = g.blocks_m[0] + g.blocks_m[1];
-    if (nb == 0) return SVAE_OK;
-    dim3 grid9(nb, (g.N + t.bn - 1) / t.bn);
-    if (int e = (t.bn == 128 ? launch_halo256<128>(sa, grid9, st, pieces, halo_rows(g, 256))
-                             : launch_halo256<64>(sa, grid9, st, pieces, halo_rows(g, 256)))) return e;
-    return check_launch("gather_halo_bf16s<256>");
-  }
-  for (int p = 0; p < 2; ++p) g.blocks_m[p] = (int)((g.M[p] + t.bm - 1) / t.bm);
-  const int bm = g.blocks_m[0] + g.blocks_m[1];
-  if (bm == 0) return SVAE_OK;
-  dim3 grid(bm, (g.N + t.bn - 1) / t.bn);
-#ifdef SVAE_ABLATION_KERNELS
-#define SVAE_ABLATION_CASE(BM_, BN_) \
-  else if (v >= 10 && v < 26 && BM_ == 128 && BN_ == 128 && pieces == 3) launch_split_dbg(sa, grid, st, v - 10);
-#else
-#define SVAE_ABLATION_CASE(BM_, BN_)
+  const SplitGeo geo = split_gather_geometry(g, code, pieces);
+  for (int p = 0; p < 2; ++p) g.blocks_m[p] = geo.blocks_m[p];
+#ifdef SVAE_ABLATION_KERNELS  // timing experiments with parts of the work removed (wrong results): python scrubvae_amd/build.py --ablation
+  if (int e = 0; launch_split_halo_diag(sa, geo, st, pieces, &e)) return e;
 #endif
+  if (geo.status) { set_error(geo.why, geo.why_arg); return geo.status; }
+  if (geo.grid_x == 0) return SVAE_OK;
+  const dim3 grid(geo.grid_x, geo.grid_y);
+  const int v = geo.v;
+  if (v >= 10 && v <= 18) return launch_split_halo_ws(sa, geo, grid, st, pieces);
+  if (v == 8 || v == 9 || v == 19 || v == 29) {
+    bool ok;
+    if (v == 29) ok = launch_halo<256, 256, 4, 2>(sa, geo, grid, st, pieces);
+    else if (v == 19) ok = launch_halo<256, 160, 8, 1>(sa, geo, grid, st, pieces);
+    else if (v == 9) ok = geo.bn == 128 ? launch_halo<256, 128, 4, 2>(sa, geo, grid, st, pieces) : launch_halo<256, 64, 4, 2>(sa, geo, grid, st, pieces);
+    else ok = geo.bn == 128 ? launch_halo<128, 128, 4, 2>(sa, geo, grid, st, pieces) : launch_halo<128, 64, 4, 2>(sa, geo, grid, st, pieces);
+    if (!ok) return split_no_instance(geo, pieces);
+    return check_launch(v == 29 ? "gather_halo_bf16s<256,256>" : v == 19 ? "gather_halo_bf16s<256,160>" : v == 9 ? "gather_halo_bf16s<256>" : "gather_gemm_bf16s");
+  }
 #define SVAE_SPLIT_CASE(BM_, BN_)                                                          \
-  if (t.bm == BM_ && t.bn == BN_) {                                                        \
+  if (geo.bm == BM_ && geo.bn == BN_) {                                                    \
     if (v == 0) launch_split_p<BM_, BN_, 2, 2, 2, 1>(sa, grid, st, pieces);                \
     else if (v == 1) launch_split_p<BM_, BN_, 2, 2, 1, 2>(sa, grid, st, pieces);           \
     else if (v == 2 && BM_ == 128) launch_split_p<128, BN_, 4, 2, 1, 2>(sa, grid, st, pieces); \
@@ -1073,9 +978,7 @@ static int launch_split_gather(SplitGatherArgs& sa, hipStream_t st, int code, in
     else if (v == 6 && BM_ == 128) launch_split_ws<128, BN_, 4, 2, 3>(sa, grid, st, pieces);  \
     else if (v == 6 && BN_ == 128) launch_split_ws<64, 128, 2, 4, 3>(sa, grid, st, pieces);   \
     else if (v == 7) launch_split_ws<BM_, BN_, 2, 2, 3>(sa, grid, st, pieces);                \
-    else if (v == 8 && BM_ == 128) { if (int e = launch_halo<BN_>(sa, grid, st, pieces, halo_rows(g, 128))) return e; } \
-    SVAE_ABLATION_CASE(BM_, BN_)                                                           \
-    else { set_error("split gather: tile code %d unsupported", code); return SVAE_ERR_SHAPE; } \
+    else return split_no_instance(geo, pieces);                                            \
   }
   SVAE_SPLIT_CASE(128, 128) else SVAE_SPLIT_CASE(128, 64) else SVAE_SPLIT_CASE(64, 128) else SVAE_SPLIT_CASE(64, 64)
 #undef SVAE_SPLIT_CASE
@@ -1104,17 +1007,18 @@ extern "C" int svae_conv_split_weights(const svae_conv_desc* d, const float* w, 
   return check_launch("split_weights");
 }
 
+// what pass `kind` of the descriptor launches with its current tile choice
+static SplitGeo split_geometry_of(const svae_conv_desc* d, int kind) {
+  GatherArgs g;
+  memset(&g, 0, sizeof(g));
+  plan_for_kind(g, d, kind);
+  return split_gather_geometry(g, d->tile[kind], 2);
+}
+
 // row tiles of the split forward launch for the descriptor's current tile choice
 extern "C" int svae_conv_fwd_stats_tiles(const svae_conv_desc* d) {
   if (validate(d)) return 0;
-  GatherArgs g;
-  memset(&g, 0, sizeof(g));
-  g.N = d->c_out;
-  build_plan(g, d, !d->transposed, d->l_out, d->l_in);
-  Tile t;
-  if (!decode_tile(d->tile[0], t)) { t = pick_tile(g.M[0], g.M[1], g.N); t.dma = 1; if (d->up2) { t.bm = 128; t.dma = 8; } }  // as launch_split_gather
-  const int bm = (t.dma == 9 || t.dma == 11 || t.dma >= 13) ? 256 : t.bm;  // (13 .. 19 and 29: 256-row tiles)
-  return (int)((g.M[0] + bm - 1) / bm + (g.M[1] + bm - 1) / bm);
+  return (int)split_geometry_of(d, 0).grid_x;
 }
 
 extern "C" int svae_conv_fwd_split(const svae_conv_desc* d, const float* x, const void* wsplit, const float* bias, float* y,
@@ -1144,28 +1048,19 @@ extern "C" int svae_conv_fwd_split_up2(const svae_conv_desc* d, const float* x, 
   sa.KB = (d->c_in + 31) / 32;
   sa.rowsA = (long long)d->batch * d->l_in;
   g.A = x; g.bias = bias; g.C = y;
-  g.Kc = d->c_in; g.ldA = d->ld_in; g.ldC = d->ld_out;
-  g.N = d->c_out;
   g.accumulate = accumulate;
   g.stats = bn_part;
-  g.up = d->up2;
   sa.up_out = up_out;
-  build_plan(g, d, /*strided=*/!d->transposed, d->l_out, d->l_in);
+  plan_for_kind(g, d, 0);
   return launch_split_gather(sa, (hipStream_t)stream, d->tile[0], pieces);
 }
 
 // row tiles / column blocks of the split data-gradient launch for the descriptor's current tile choice
 extern "C" int svae_conv_dgrad_stats_tiles(const svae_conv_desc* d, int* col_blocks) {
   if (validate(d)) return 0;
-  GatherArgs g;
-  memset(&g, 0, sizeof(g));
-  g.N = d->c_in;
-  build_plan(g, d, d->transposed != 0, d->l_in, d->l_out);
-  Tile t;
-  if (!decode_tile(d->tile[1], t)) { t = pick_tile(g.M[0], g.M[1], g.N); t.dma = 1; }
-  const int bm = (t.dma == 9 || t.dma == 11 || t.dma >= 13) ? 256 : t.bm;
-  if (col_blocks) *col_blocks = t.dma == 19 ? (g.N + 159) / 160 : (t.dma == 29 ? (g.N + 255) / 256 : (g.N + t.bn - 1) / t.bn);
-  return (int)((g.M[0] + bm - 1) / bm + (g.M[1] + bm - 1) / bm);
+  const SplitGeo s = split_geometry_of(d, 1);
+  if (col_blocks) *col_blocks = (int)s.grid_y;
+  return (int)s.grid_x;
 }
 
 extern "C" int svae_conv_dgrad_split(const svae_conv_desc* d, const float* dy, const void* wsplit, float* dx, int accumulate,
@@ -1187,15 +1082,13 @@ extern "C" int svae_conv_dgrad_split_bn(const svae_conv_desc* d, const float* dy
   sa.KB = (d->c_out + 31) / 32;
   sa.rowsA = (long long)d->batch * d->l_out;
   g.A = dy; g.bias = nullptr; g.C = dx;
-  g.Kc = d->c_out; g.ldA = d->ld_out; g.ldC = d->ld_in;
-  g.N = d->c_in;
   g.accumulate = accumulate;
   if (f) {
     SVAE_REQUIRE(f->x && f->part && (!f->scale || f->shift) && (!f->mean || f->rstd), SVAE_ERR_ARG, "conv_dgrad_split_bn: bad fuse descriptor");
     g.stats = f->part; g.bn_x = f->x; g.bn_scale = f->scale; g.bn_shift = f->shift; g.bn_mean = f->mean; g.bn_rstd = f->rstd;
     g.bn_alpha = f->alpha; g.bn_dalpha = f->dalpha_part;
   }
-  build_plan(g, d, /*strided=*/d->transposed != 0, d->l_in, d->l_out);
+  plan_for_kind(g, d, 1);
   return launch_split_gather(sa, (hipStream_t)stream, d->tile[1], pieces);
 }
 
@@ -1204,22 +1097,11 @@ extern "C" int svae_conv_dgrad_split_bn(const svae_conv_desc* d, const float* dy
 extern "C" int svae_conv_split_tile(const svae_conv_desc* d, int kind, int* bm, int* bn, int* variant, int* rmax) {
   if (int e = validate(d)) return e;
   SVAE_REQUIRE(bm && bn && variant && rmax && (kind == 0 || kind == 1), SVAE_ERR_ARG, "conv_split_tile: bad args");
-  GatherArgs g;
-  memset(&g, 0, sizeof(g));
-  if (kind == 0) { g.N = d->c_out; build_plan(g, d, !d->transposed, d->l_out, d->l_in); }
-  else { g.N = d->c_in; build_plan(g, d, d->transposed != 0, d->l_in, d->l_out); }
-  Tile t;
-  if (!decode_tile(d->tile[kind], t)) { t = pick_tile(g.M[0], g.M[1], g.N); t.dma = 1; if (d->up2 && kind == 0) { t.bm = 128; t.dma = 8; } }
-  *bm = t.bm; *bn = t.bn; *variant = t.dma; *rmax = 0;
-  if (t.dma == 8) { const int r = halo_rows(g, 128); *rmax = r <= 160 ? 160 : 264; }
-  if (t.dma == 9) { const int r = halo_rows(g, 256); *bm = 256; *rmax = r <= 320 ? 320 : 528; }
-  if (t.dma == 10 || t.dma == 12) { const int r = halo_rows(g, 128); *rmax = r <= 160 ? 160 : 264; }
-  if (t.dma == 11) { const int r = halo_rows(g, 256); *bm = 256; *rmax = r <= 264 ? 264 : 320; }
-  if (t.dma == 13) { *bm = 256; *rmax = 264; }
-  if (t.dma == 14 || t.dma == 15) { const int r = halo_rows(g, 256); *bm = 256; *rmax = r <= 264 ? 264 : 320; }
-  if (t.dma >= 16 && t.dma <= 18) { const int r = halo_rows(g, 256); *bm = 256; *rmax = r <= 264 ? 264 : 320; }
-  if (t.dma == 19) { const int r = halo_rows(g, 256); *bm = 256; *bn = 160; *rmax = r <= 320 ? 320 : 528; }
-  if (t.dma == 29) { *bm = 256; *bn = 256; *rmax = 320; }
+  const SplitGeo s = split_geometry_of(d, kind);  // filled also where the launch would refuse the geometry (s.status): the tuner and
+  *variant = s.v;                                  // the kernel's printed name ask before they launch
+  *bm = (s.v >= 20 && s.v != 29) ? s.code_bm : s.bm;  // (the ablation build's diagnostic variants report the row field of their code)
+  *bn = s.bn;
+  *rmax = s.rmax;
   return SVAE_OK;
 }
 

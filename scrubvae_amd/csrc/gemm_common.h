@@ -107,6 +107,20 @@ inline void build_plan(GatherArgs& g, const svae_conv_desc* d, bool strided, int
   }
 }
 
+// The gather GEMM of pass `kind` -- 0: forward (rows of y from x), 1: data gradient (rows of dx from dy; conv: lo = (li + pad -
+// t*dil)/stride, fractional; convT: lo = li*stride + t*dil - pad, strided): its dimensions, leading dimensions and plan
+inline void plan_for_kind(GatherArgs& g, const svae_conv_desc* d, int kind) {
+  if (kind == 0) {
+    g.Kc = d->c_in; g.N = d->c_out; g.ldA = d->ld_in; g.ldC = d->ld_out;
+    g.up = d->up2;
+    build_plan(g, d, /*strided=*/!d->transposed, d->l_out, d->l_in);
+  } else {
+    g.Kc = d->c_out; g.N = d->c_in; g.ldA = d->ld_out; g.ldC = d->ld_in;
+    g.up = 0;  // the gradient with respect to the upsampled input
+    build_plan(g, d, /*strided=*/d->transposed != 0, d->l_in, d->l_out);
+  }
+}
+
 // true when the tap tables are the arithmetic progressions base0 + i * bstep / w0 + i * wstep (always, by construction: checked)
 inline bool plan_is_affine(const GatherArgs& g) {
   for (int p = 0; p < g.n_phase; ++p)
@@ -147,7 +161,7 @@ inline Tile pick_tile(long long M0, long long M1, int N) {
 
 inline bool decode_tile(int code, Tile& t) {
   if (code <= 0) return false;
-  t.dma = code / 1000000;  // VBBBNNN: kernel variant (fp32 gather: 1 = LDS-DMA staging; split-bf16: see gemm_bf16s.hip)
+  t.dma = code / 1000000;  // VBBBNNN: kernel variant (fp32 gather: 1 = LDS-DMA staging; split-bf16: see split_gather.h)
   code %= 1000000;
   t.bm = code / 1000;
   t.bn = code % 1000;

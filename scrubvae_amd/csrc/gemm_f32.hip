@@ -935,32 +935,14 @@ static int launch_gather_auto(GatherArgs& g, hipStream_t st, int override_code, 
 
 using namespace svae;
 
-extern "C" int svae_conv_fwd(const svae_conv_desc* d, const float* x, const float* w, const float* bias, float* y,
-                             int accumulate, void* stream) {
-  if (int e = validate(d)) return e;
-  SVAE_REQUIRE(!d->up2, SVAE_ERR_SHAPE, "conv_fwd: the fused x2 upsample of the input (up2) exists in the split-precision halo kernels only");
-  SVAE_REQUIRE(x && w && y, SVAE_ERR_ARG, "conv_fwd: null pointer");
-  SVAE_REQUIRE(aligned16(x) && aligned16(w) && aligned16(y), SVAE_ERR_ALIGN, "conv_fwd: pointers must be 16-byte aligned");
-  GatherArgs g;
-  memset(&g, 0, sizeof(g));
-  g.A = x; g.W = w; g.bias = bias; g.C = y;
-  g.Kc = d->c_in; g.ldA = d->ld_in; g.ldC = d->ld_out; g.ldW = d->c_out;
-  g.w_tap_stride = (long long)d->c_in * d->c_out;
-  g.N = d->c_out;
-  g.accumulate = accumulate;
-  build_plan(g, d, /*strided=*/!d->transposed, d->l_out, d->l_in);
-  return launch_gather_auto<false>(g, (hipStream_t)stream, d->tile[0]);
-}
-
-// ---- the same two calls with an optional split-K workspace: problems with few output tiles and a long reduction
+// ---- forward / data gradient, with an optional split-K workspace: problems with few output tiles and a long reduction
 // (the Linear heads: M = batch rows, N = z) are split over K into `svae_conv_splitk_workspace` bytes of partial
-// tiles that are summed in a fixed order.  ws == NULL or too small: identical to svae_conv_fwd / svae_conv_dgrad.
+// tiles that are summed in a fixed order.  ws == NULL or too small: no split (svae_conv_fwd / svae_conv_dgrad).
 extern "C" size_t svae_conv_splitk_workspace(const svae_conv_desc* d, int kind) {
   if (validate(d) || (kind != 0 && kind != 1)) return 0;
   GatherArgs g;
   memset(&g, 0, sizeof(g));
-  if (kind == 0) { g.Kc = d->c_in; g.N = d->c_out; build_plan(g, d, !d->transposed, d->l_out, d->l_in); }
-  else { g.Kc = d->c_out; g.N = d->c_in; build_plan(g, d, d->transposed != 0, d->l_in, d->l_out); }
+  plan_for_kind(g, d, kind);
   const int ks = splitk_factor(g, 64, 64);
   return ks >= 2 ? (size_t)ks * g.M[0] * g.N * sizeof(float) : 0;
 }
@@ -974,12 +956,16 @@ extern "C" int svae_conv_fwd_ws(const svae_conv_desc* d, const float* x, const f
   GatherArgs g;
   memset(&g, 0, sizeof(g));
   g.A = x; g.W = w; g.bias = bias; g.C = y;
-  g.Kc = d->c_in; g.ldA = d->ld_in; g.ldC = d->ld_out; g.ldW = d->c_out;
+  g.ldW = d->c_out;
   g.w_tap_stride = (long long)d->c_in * d->c_out;
-  g.N = d->c_out;
   g.accumulate = accumulate;
-  build_plan(g, d, /*strided=*/!d->transposed, d->l_out, d->l_in);
+  plan_for_kind(g, d, 0);
   return launch_gather_auto<false>(g, (hipStream_t)stream, d->tile[0], ws, ws_bytes);
+}
+
+extern "C" int svae_conv_fwd(const svae_conv_desc* d, const float* x, const float* w, const float* bias, float* y,
+                             int accumulate, void* stream) {
+  return svae_conv_fwd_ws(d, x, w, bias, y, accumulate, nullptr, 0, stream);
 }
 
 extern "C" int svae_conv_dgrad_ws(const svae_conv_desc* d, const float* dy, const float* w, float* dx, int accumulate, void* ws,
@@ -990,29 +976,16 @@ extern "C" int svae_conv_dgrad_ws(const svae_conv_desc* d, const float* dy, cons
   GatherArgs g;
   memset(&g, 0, sizeof(g));
   g.A = dy; g.W = w; g.bias = nullptr; g.C = dx;
-  g.Kc = d->c_out; g.ldA = d->ld_out; g.ldC = d->ld_in; g.ldW = d->c_out;
+  g.ldW = d->c_out;
   g.w_tap_stride = (long long)d->c_in * d->c_out;
-  g.N = d->c_in;
   g.accumulate = accumulate;
-  build_plan(g, d, /*strided=*/d->transposed != 0, d->l_in, d->l_out);
+  plan_for_kind(g, d, 1);
   return launch_gather_auto<true>(g, (hipStream_t)stream, d->tile[1], ws, ws_bytes);
 }
 
 extern "C" int svae_conv_dgrad(const svae_conv_desc* d, const float* dy, const float* w, float* dx, int accumulate,
                                void* stream) {
-  if (int e = validate(d)) return e;
-  SVAE_REQUIRE(dy && w && dx, SVAE_ERR_ARG, "conv_dgrad: null pointer");
-  SVAE_REQUIRE(aligned16(dy) && aligned16(w) && aligned16(dx), SVAE_ERR_ALIGN, "conv_dgrad: pointers must be 16-byte aligned");
-  GatherArgs g;
-  memset(&g, 0, sizeof(g));
-  g.A = dy; g.W = w; g.bias = nullptr; g.C = dx;
-  g.Kc = d->c_out; g.ldA = d->ld_out; g.ldC = d->ld_in; g.ldW = d->c_out;
-  g.w_tap_stride = (long long)d->c_in * d->c_out;
-  g.N = d->c_in;
-  g.accumulate = accumulate;
-  // conv: lo = (li + pad - t*dil)/stride (fractional); convT: lo = li*stride + t*dil - pad (strided)
-  build_plan(g, d, /*strided=*/d->transposed != 0, d->l_in, d->l_out);
-  return launch_gather_auto<true>(g, (hipStream_t)stream, d->tile[1]);
+  return svae_conv_dgrad_ws(d, dy, w, dx, accumulate, nullptr, 0, stream);
 }
 
 namespace svae {
@@ -1277,8 +1250,7 @@ extern "C" int svae_conv_tile(const svae_conv_desc* d, int kind, int* bm, int* b
   }
   GatherArgs g;
   memset(&g, 0, sizeof(g));
-  if (kind == 0) { g.N = d->c_out; build_plan(g, d, !d->transposed, d->l_out, d->l_in); }
-  else { g.N = d->c_in; build_plan(g, d, d->transposed != 0, d->l_in, d->l_out); }
+  plan_for_kind(g, d, kind);
   Tile t;
   if (!decode_tile(d->tile[kind], t)) t = pick_tile(g.M[0], g.M[1], g.N);
   *bm = t.bm + 1000 * t.dma;  // + 1000 * kernel variant (fp32: 1 = LDS-DMA staging)

@@ -1142,116 +1142,82 @@ __global__ __launch_bounds__(768) void gather_halo_ws4m_bf16s_kernel(const Split
                                            tile_x, tile_y);
 }
 
-// V = 10 / 11: the wave-specialised halo kernel (8 consumer + 2 producer waves) on 128- / 256-row tiles (row field of the code: 128).
-// Instantiated where two image buffers + two weight stages fit the 160 KiB of LDS.
-template <int BM, int BN>
-static int launch_halo_ws(const SplitGatherArgs& sa, dim3 grid, hipStream_t st, int pieces, int rows) {
-  const dim3 block(64 * 10);
-  if (pieces != 3 && pieces != 2 && pieces != SVAE_PIECES_F16X2) { set_error("split gather: the halo kernels are built for 2 or 3 pieces"); return SVAE_ERR_SHAPE; }
-#define SVAE_HWS(P_, R_) hipLaunchKernelGGL((gather_halo_ws_bf16s_kernel<BM, BN, P_, 4, 2, R_>), grid, block, 0, st, sa)
-#define SVAE_HWSH(R_) hipLaunchKernelGGL((gather_halo_ws_bf16s_kernel<BM, BN, 2, 4, 2, R_, 0, false, 2, true>), grid, block, 0, st, sa)
-  if constexpr (BM == 128) {
-    if (rows <= 160) { if (pieces == 3) SVAE_HWS(3, 160); else if (pieces == 2) SVAE_HWS(2, 160); else SVAE_HWSH(160); }
-    else if (rows <= 264) { if (pieces == 3) SVAE_HWS(3, 264); else if (pieces == 2) SVAE_HWS(2, 264); else SVAE_HWSH(264); }
-    else { set_error("split gather: halo image of %d rows does not fit", rows); return SVAE_ERR_SHAPE; }
-  } else {
-    if (rows <= 264) { if (pieces == 3) SVAE_HWS(3, 264); else if (pieces == 2) SVAE_HWS(2, 264); else SVAE_HWSH(264); }
-    else if (rows <= 320 && pieces == 2) SVAE_HWS(2, 320);
-    else if (rows <= 320 && pieces == SVAE_PIECES_F16X2) SVAE_HWSH(320);
-    else { set_error("split gather: 256-row halo image of %d rows does not fit twice", rows); return SVAE_ERR_SHAPE; }
+// gather_halo_ws_bf16s_kernel (V = 10 .. 15; the variants and what exists of them: split_gather_geometry): the instance for
+// (pieces, fp16, image rows).  NB: weight-tile buffers; WR x WC consumer waves + 2 producers.  Corners that are not built
+// (they do not fit the LDS; the resolver refuses them) stay uninstantiated: false.
+template <int BM, int BN, int WR, int WC, int NB, bool PIPE, int P, bool H>
+static bool launch_halo_ws_rows(const SplitGatherArgs& sa, const SplitGeo& geo, dim3 grid, hipStream_t st) {
+  const dim3 block(64 * (WR * WC + 2));
+  constexpr int R0 = BM == 128 ? 160 : 264, R1 = BM == 128 ? 264 : 320;
+  constexpr bool HAS_R1 = BM == 128 || (P == 2 && (NB == 2 || WR == 2));
+  if (geo.rmax == R0) {
+    hipLaunchKernelGGL((gather_halo_ws_bf16s_kernel<BM, BN, P, WR, WC, R0, 0, PIPE, NB, H>), grid, block, 0, st, sa);
+    return true;
   }
-#undef SVAE_HWS
-#undef SVAE_HWSH
-  return SVAE_OK;
+  if constexpr (HAS_R1) {
+    hipLaunchKernelGGL((gather_halo_ws_bf16s_kernel<BM, BN, P, WR, WC, R1, 0, PIPE, NB, H>), grid, block, 0, st, sa);
+    return true;
+  }
+  return false;
 }
 
-// V = 12 / 13: the same kernel with three weight-tile buffers (the producers request two stages ahead): 2 pieces on BN = 128 or 64,
-// 3 pieces on BN = 64 (LDS)
-template <int BM, int BN>
-static int launch_halo_ws_pipe(const SplitGatherArgs& sa, dim3 grid, hipStream_t st, int pieces, int rows) {
-  const dim3 block(64 * 10);
-  if (pieces == SVAE_PIECES_F16X2) {  // three weight buffers, fp16 pieces
-#define SVAE_HWPH(R_) hipLaunchKernelGGL((gather_halo_ws_bf16s_kernel<BM, BN, 2, 4, 2, R_, 0, false, 3, true>), grid, block, 0, st, sa)
-    constexpr int R0h = BM == 128 ? 160 : 264;
-    if (rows <= R0h) SVAE_HWPH(R0h);
-    else if (BM == 128 && rows <= 264) SVAE_HWPH(264);
-    else { set_error("split gather: halo image of %d rows does not fit", rows); return SVAE_ERR_SHAPE; }
-#undef SVAE_HWPH
-    return SVAE_OK;
+template <int BM, int BN, int WR, int WC, int NB, bool PIPE = false>
+static bool launch_halo_ws(const SplitGatherArgs& sa, const SplitGeo& geo, dim3 grid, hipStream_t st, int pieces) {
+  if (pieces == SVAE_PIECES_F16X2) return launch_halo_ws_rows<BM, BN, WR, WC, NB, PIPE, 2, true>(sa, geo, grid, st);
+  if (pieces == 2) return launch_halo_ws_rows<BM, BN, WR, WC, NB, PIPE, 2, false>(sa, geo, grid, st);
+  if constexpr (WR == 4 && !(NB == 3 && BN != 64)) {  // 3 pieces: 8 consumer waves; with three weight buffers on 64 columns
+    if (pieces == 3) return launch_halo_ws_rows<BM, BN, WR, WC, NB, PIPE, 3, false>(sa, geo, grid, st);
   }
-  if (pieces != 3 && pieces != 2) { set_error("split gather: the halo kernels are built for 2 or 3 pieces"); return SVAE_ERR_SHAPE; }
-  if (pieces == 3 && BN != 64) { set_error("split gather: three weight buffers with 3 pieces exist for 64-column tiles only"); return SVAE_ERR_SHAPE; }
-#define SVAE_HWP(P_, R_) hipLaunchKernelGGL((gather_halo_ws_bf16s_kernel<BM, BN, P_, 4, 2, R_, 0, false, 3>), grid, block, 0, st, sa)
-  constexpr int R0 = BM == 128 ? 160 : 264;
-  if (rows <= R0) {
-    if (pieces == 2) SVAE_HWP(2, R0);
-    else if constexpr (BN == 64) SVAE_HWP(3, R0);
-  } else if (BM == 128 && rows <= 264) {
-    if (pieces == 2) SVAE_HWP(2, 264);
-    else if constexpr (BN == 64) SVAE_HWP(3, 264);
-  } else { set_error("split gather: halo image of %d rows does not fit", rows); return SVAE_ERR_SHAPE; }
-#undef SVAE_HWP
-  return SVAE_OK;
+  return false;
 }
 
-// V = 14 / 15: FOUR consumer waves with 128 x 64 wave tiles (one per SIMD, 256 registers each) + 2 producers on the 256 x 128 tile:
-// every operand fragment feeds 4 or 2 MFMA groups instead of 2, i.e. 25 % fewer LDS fragment bytes per MFMA -- the resource the
-// ablations show is NOT overlapped with the matrix pipe.  14: compiler-scheduled pipeline, 15: pinned (sched_barrier).  2 pieces only.
-template <bool PIPE_>
-static int launch_halo_ws_fat(const SplitGatherArgs& sa, dim3 grid, hipStream_t st, int pieces, int rows) {
-  const dim3 block(64 * 6);
-  if (pieces != 2 && pieces != SVAE_PIECES_F16X2) { set_error("split gather: the 128 x 64 wave tiles are built for 2 pieces"); return SVAE_ERR_SHAPE; }
-#define SVAE_HWF(R_, H_) hipLaunchKernelGGL((gather_halo_ws_bf16s_kernel<256, 128, 2, 2, 2, R_, 0, PIPE_, 3, H_>), grid, block, 0, st, sa)
-  if (rows <= 264) { if (pieces == 2) SVAE_HWF(264, false); else SVAE_HWF(264, true); }
-  else if (rows <= 320) { if (pieces == 2) SVAE_HWF(320, false); else SVAE_HWF(320, true); }
-  else { set_error("split gather: 256-row halo image of %d rows does not fit", rows); return SVAE_ERR_SHAPE; }
-#undef SVAE_HWF
-  return SVAE_OK;
-}
-
-// V = 16 / 17: gather_halo_ws4_bf16s_kernel (8 consumer + 4 loader waves, 256-row tiles; row field of the code: 128) with / without
-// the quarter-stage stagger of the consumers' second half;  V = 18: the same kernel on v_mfma_f32_16x16x32 (gather_halo_ws4m_bf16s_kernel).  Two pieces (bf16 or fp16) only.  The raw staging ring holds
-// three slices of ceil(image rows / ntaps) rows: 88 rows beside 264-row images (ntaps >= 3), 64 beside 320-row images (ntaps >= 5).
-static int ws4_slice_rows(const GatherArgs& g, int rmax) {
-  int worst = 0;
-  for (int p = 0; p < 2; ++p) {
-    if (g.M[p] <= 0 || g.ntaps[p] <= 0) continue;
-    const int sr = (((rmax + g.ntaps[p] - 1) / g.ntaps[p]) + 7) & ~7;
-    worst = sr > worst ? sr : worst;
-  }
-  return worst;
-}
+// gather_halo_ws4_bf16s_kernel / gather_halo_ws4m_bf16s_kernel (V = 16 / 17 / 18)
 template <int BN, bool STAG, bool M16 = false>
-static int launch_halo_ws4(const SplitGatherArgs& sa, dim3 grid, hipStream_t st, int pieces, int rows) {
+static bool launch_halo_ws4(const SplitGatherArgs& sa, const SplitGeo& geo, dim3 grid, hipStream_t st, int pieces) {
   const dim3 block(768);
-  if (pieces != 2 && pieces != SVAE_PIECES_F16X2) { set_error("split gather: the 12-wave halo kernel is built for 2 pieces"); return SVAE_ERR_SHAPE; }
-  const int rmax = rows <= 264 ? 264 : 320;
-  if (rows > 320 || ws4_slice_rows(sa.g, rmax) > (rmax == 264 ? 88 : 64)) {
-    set_error("split gather: 256-row halo image of %d rows / its raw slices do not fit", rows);
-    return SVAE_ERR_SHAPE;
-  }
 #define SVAE_HW4(R_, S_, H_)                                                                                         \
   do {                                                                                                               \
     if constexpr (M16) hipLaunchKernelGGL((gather_halo_ws4m_bf16s_kernel<256, BN, R_, S_, H_>), grid, block, 0, st, sa); \
     else hipLaunchKernelGGL((gather_halo_ws4_bf16s_kernel<256, BN, R_, S_, H_, STAG>), grid, block, 0, st, sa);       \
   } while (0)
-  if (pieces == 2) { if (rmax == 264) SVAE_HW4(264, 88, false); else SVAE_HW4(320, 64, false); }
-  else { if (rmax == 264) SVAE_HW4(264, 88, true); else SVAE_HW4(320, 64, true); }
+  if (pieces == 2) { if (geo.rmax == 264) SVAE_HW4(264, 88, false); else SVAE_HW4(320, 64, false); }
+  else if (pieces == SVAE_PIECES_F16X2) { if (geo.rmax == 264) SVAE_HW4(264, 88, true); else SVAE_HW4(320, 64, true); }
+  else return false;
 #undef SVAE_HW4
-  return SVAE_OK;
+  return true;
 }
 
-int launch_split_halo_ws(SplitGatherArgs& sa, hipStream_t st, const Tile& t, int code, int pieces, bool* handled) {
-  GatherArgs& g = sa.g;
-  const int v = t.dma;
-  *handled = true;
+int launch_split_halo_ws(const SplitGatherArgs& sa, const SplitGeo& geo, dim3 grid, hipStream_t st, int pieces) {
+  const bool wide = geo.bn == 128;
+  bool ok = false;
+  switch (geo.v) {
+    case 10: ok = wide ? launch_halo_ws<128, 128, 4, 2, 2>(sa, geo, grid, st, pieces) : launch_halo_ws<128, 64, 4, 2, 2>(sa, geo, grid, st, pieces); break;
+    case 11: ok = wide ? launch_halo_ws<256, 128, 4, 2, 2>(sa, geo, grid, st, pieces) : launch_halo_ws<256, 64, 4, 2, 2>(sa, geo, grid, st, pieces); break;
+    case 12: ok = wide ? launch_halo_ws<128, 128, 4, 2, 3>(sa, geo, grid, st, pieces) : launch_halo_ws<128, 64, 4, 2, 3>(sa, geo, grid, st, pieces); break;
+    case 13: ok = wide ? launch_halo_ws<256, 128, 4, 2, 3>(sa, geo, grid, st, pieces) : launch_halo_ws<256, 64, 4, 2, 3>(sa, geo, grid, st, pieces); break;
+    case 14: ok = launch_halo_ws<256, 128, 2, 2, 3, false>(sa, geo, grid, st, pieces); break;
+    case 15: ok = launch_halo_ws<256, 128, 2, 2, 3, true>(sa, geo, grid, st, pieces); break;
+    case 16: ok = wide ? launch_halo_ws4<128, true>(sa, geo, grid, st, pieces) : launch_halo_ws4<64, true>(sa, geo, grid, st, pieces); break;
+    case 17: ok = wide ? launch_halo_ws4<128, false>(sa, geo, grid, st, pieces) : launch_halo_ws4<64, false>(sa, geo, grid, st, pieces); break;
+    case 18: ok = wide ? launch_halo_ws4<128, true, true>(sa, geo, grid, st, pieces) : launch_halo_ws4<64, true, true>(sa, geo, grid, st, pieces); break;
+    default: break;
+  }
+  if (!ok) return split_no_instance(geo, pieces);
+  return check_launch(geo.v >= 16 ? "gather_halo_ws4_bf16s" : "gather_halo_ws_bf16s");
+}
+
 #ifdef SVAE_ABLATION_KERNELS
-  if ((v == 37 || v == 38) && (pieces == 2 || pieces == SVAE_PIECES_F16X2)) {  // stamped gather_halo_ws4_bf16s_kernel (tools/stamp_halo.py)
-    for (int p = 0; p < 2; ++p) g.blocks_m[p] = (int)((g.M[p] + 255) / 256);
-    const int nb = g.blocks_m[0] + g.blocks_m[1];
-    if (nb == 0) return SVAE_OK;
-    dim3 gridw(nb, (g.N + 127) / 128), block(768);
-    if (halo_rows(g, 256) > 264) { set_error("ablation: image does not fit"); return SVAE_ERR_SHAPE; }
+bool launch_split_halo_diag(const SplitGatherArgs& sa, const SplitGeo& geo, hipStream_t st, int pieces, int* e) {
+  const GatherArgs& g = sa.g;
+  const int v = geo.v;
+  const bool stamped = (v == 37 || v == 38) && (pieces == 2 || pieces == SVAE_PIECES_F16X2);  // stamped gather_halo_ws4_bf16s_kernel (tools/stamp_halo.py)
+  const bool dbg = ((v >= 20 && v < 28) || v == 36) && (pieces == 3 || pieces == 2);  // timing experiments on the 256 x 128 wave-specialised halo kernel: V = 20 + DBG
+  if (!stamped && !dbg) return false;
+  *e = SVAE_OK;
+  if (geo.grid_x == 0) return true;
+  const dim3 gridw(geo.grid_x, (g.N + 127) / 128), block(stamped ? 768 : 640);
+  if (halo_rows(g, 256) > 264) { set_error("ablation: image does not fit"); *e = SVAE_ERR_SHAPE; return true; }
+  if (stamped) {
     if (v == 37) {
       if (pieces == 2) hipLaunchKernelGGL((gather_halo_ws4_bf16s_kernel<256, 128, 264, 88, false, true, 16>), gridw, block, 0, st, sa);
       else hipLaunchKernelGGL((gather_halo_ws4_bf16s_kernel<256, 128, 264, 88, true, true, 16>), gridw, block, 0, st, sa);
@@ -1259,58 +1225,17 @@ int launch_split_halo_ws(SplitGatherArgs& sa, hipStream_t st, const Tile& t, int
       if (pieces == 2) hipLaunchKernelGGL((gather_halo_ws4_bf16s_kernel<256, 128, 264, 88, false, false, 16>), gridw, block, 0, st, sa);
       else hipLaunchKernelGGL((gather_halo_ws4_bf16s_kernel<256, 128, 264, 88, true, false, 16>), gridw, block, 0, st, sa);
     }
-    return check_launch("gather_halo_ws4_bf16s<stamps>");
+    *e = check_launch("gather_halo_ws4_bf16s<stamps>");
+    return true;
   }
-  if (((v >= 20 && v < 28) || v == 36) && (pieces == 3 || pieces == 2)) {  // timing experiments on the 256 x 128 wave-specialised halo kernel: V = 20 + DBG
-    for (int p = 0; p < 2; ++p) g.blocks_m[p] = (int)((g.M[p] + 255) / 256);
-    const int nb = g.blocks_m[0] + g.blocks_m[1];
-    if (nb == 0) return SVAE_OK;
-    dim3 gridw(nb, (g.N + 127) / 128), block(640);
-    if (halo_rows(g, 256) > 264) { set_error("ablation: image does not fit"); return SVAE_ERR_SHAPE; }
 #define SVAE_HD(D_) case D_: if (pieces == 3) hipLaunchKernelGGL((gather_halo_ws_bf16s_kernel<256, 128, 3, 4, 2, 264, D_>), gridw, block, 0, st, sa); \
                              else hipLaunchKernelGGL((gather_halo_ws_bf16s_kernel<256, 128, 2, 4, 2, 264, D_, false, 3>), gridw, block, 0, st, sa); break;
-    switch (v - 20) { SVAE_HD(0) SVAE_HD(1) SVAE_HD(2) SVAE_HD(3) SVAE_HD(4) SVAE_HD(5) SVAE_HD(6) SVAE_HD(7) SVAE_HD(16) default: break; }
+  switch (v - 20) { SVAE_HD(0) SVAE_HD(1) SVAE_HD(2) SVAE_HD(3) SVAE_HD(4) SVAE_HD(5) SVAE_HD(6) SVAE_HD(7) SVAE_HD(16) default: break; }
 #undef SVAE_HD
-    return check_launch("gather_halo_ws_bf16s<dbg>");
-  }
-#endif
-  if (v == 16 || v == 17 || v == 18) {
-    if (t.bm != 128 || (t.bn != 128 && t.bn != 64)) { set_error("split gather: tile code %d unsupported", code); return SVAE_ERR_SHAPE; }
-    for (int p = 0; p < 2; ++p) g.blocks_m[p] = (int)((g.M[p] + 255) / 256);
-    const int nb = g.blocks_m[0] + g.blocks_m[1];
-    if (nb == 0) return SVAE_OK;
-    dim3 gridw(nb, (g.N + t.bn - 1) / t.bn);
-    const int rows = halo_rows(g, 256);
-    if (!plan_is_affine(g)) { set_error("split gather: tap tables are not arithmetic progressions"); return SVAE_ERR_SHAPE; }
-    int e;
-    if (v == 16) e = t.bn == 128 ? launch_halo_ws4<128, true>(sa, gridw, st, pieces, rows) : launch_halo_ws4<64, true>(sa, gridw, st, pieces, rows);
-    else if (v == 18) e = t.bn == 128 ? launch_halo_ws4<128, true, true>(sa, gridw, st, pieces, rows) : launch_halo_ws4<64, true, true>(sa, gridw, st, pieces, rows);
-    else e = t.bn == 128 ? launch_halo_ws4<128, false>(sa, gridw, st, pieces, rows) : launch_halo_ws4<64, false>(sa, gridw, st, pieces, rows);
-    if (e) return e;
-    return check_launch("gather_halo_ws4_bf16s");
-  }
-  if (v >= 10 && v <= 15) {
-    if (t.bm != 128 || (v >= 14 && t.bn != 128)) { set_error("split gather: tile code %d unsupported", code); return SVAE_ERR_SHAPE; }
-    const int bmr = (v == 11 || v >= 13) ? 256 : 128;
-    for (int p = 0; p < 2; ++p) g.blocks_m[p] = (int)((g.M[p] + bmr - 1) / bmr);
-    const int nb = g.blocks_m[0] + g.blocks_m[1];
-    if (nb == 0) return SVAE_OK;
-    dim3 gridw(nb, (g.N + t.bn - 1) / t.bn);
-    const int rows = halo_rows(g, bmr);
-    if (!plan_is_affine(g)) { set_error("split gather: tap tables are not arithmetic progressions"); return SVAE_ERR_SHAPE; }
-    int e;
-    if (v == 10) e = t.bn == 128 ? launch_halo_ws<128, 128>(sa, gridw, st, pieces, rows) : launch_halo_ws<128, 64>(sa, gridw, st, pieces, rows);
-    else if (v == 11) e = t.bn == 128 ? launch_halo_ws<256, 128>(sa, gridw, st, pieces, rows) : launch_halo_ws<256, 64>(sa, gridw, st, pieces, rows);
-    else if (v == 12) e = t.bn == 128 ? launch_halo_ws_pipe<128, 128>(sa, gridw, st, pieces, rows) : launch_halo_ws_pipe<128, 64>(sa, gridw, st, pieces, rows);
-    else if (v == 14) e = launch_halo_ws_fat<false>(sa, gridw, st, pieces, rows);
-    else if (v == 15) e = launch_halo_ws_fat<true>(sa, gridw, st, pieces, rows);
-    else e = t.bn == 128 ? launch_halo_ws_pipe<256, 128>(sa, gridw, st, pieces, rows) : launch_halo_ws_pipe<256, 64>(sa, gridw, st, pieces, rows);
-    if (e) return e;
-    return check_launch("gather_halo_ws_bf16s");
-  }
-  *handled = false;
-  return SVAE_OK;
+  *e = check_launch("gather_halo_ws_bf16s<dbg>");
+  return true;
 }
+#endif
 
 }  // namespace svae
 

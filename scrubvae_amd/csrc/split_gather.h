@@ -1,6 +1,7 @@
 // Shared by the forward / data-gradient translation units of the split-precision implicit GEMM (gemm_bf16s.hip: per-tap gather
 // kernels, the 8-wave halo kernel, dispatch and C entry points; halo_ws_bf16s.hip: the wave-specialised halo kernels): launch
-// arguments, the epilogue (bias, accumulate, fused BatchNorm sums), the halo-image row bound.
+// arguments, the epilogue (bias, accumulate, fused BatchNorm sums), the halo-image row bound, and what a tile code launches
+// (split_gather_geometry, with the list of the variants).
 #pragma once
 #include "split_common.h"
 
@@ -129,8 +130,167 @@ inline int halo_rows(const GatherArgs& g, int bm) {
   return worst;
 }
 
-// wave-specialised halo kernels (halo_ws_bf16s.hip): tile codes V = 10 .. 18 (and the diagnostic variants of the ablation build).
-// Returns SVAE_OK / an error; *handled = false when the code is none of theirs.
-int launch_split_halo_ws(SplitGatherArgs& sa, hipStream_t st, const Tile& t, int code, int pieces, bool* handled);
+// raw staging ring of the 12-wave halo kernels (V = 16 .. 18): three slices of ceil(image rows / ntaps) rows (rounded up to 8) each
+inline int ws4_slice_rows(const GatherArgs& g, int rmax) {
+  int worst = 0;
+  for (int p = 0; p < 2; ++p) {
+    if (g.M[p] <= 0 || g.ntaps[p] <= 0) continue;
+    const int sr = (((rmax + g.ntaps[p] - 1) / g.ntaps[p]) + 7) & ~7;
+    worst = sr > worst ? sr : worst;
+  }
+  return worst;
+}
+
+// ---- The split forward / data-gradient launch of a tile code, resolved in ONE place: the launchers (launch_split_gather,
+// launch_split_halo_ws) and the introspection calls (svae_conv_fwd_stats_tiles, svae_conv_dgrad_stats_tiles,
+// svae_conv_split_tile) all read this.  A new variant is one case here and one launch line.
+//
+// Tile code V * 1000000 + BM * 1000 + BN (svae_conv_desc.tile[0 / 1]; BM, BN in {64, 128}); a code that does not decode (0) means
+// the heuristic tile (pick_tile) on V = 1, and 8128NNN for a forward with the fused x2 upsample (g.up).  The variants:
+//   0 / 1   gather_gemm_bf16s_kernel: 4 waves, double-buffered LDS / single LDS buffer
+//   2 / 3   the same with 8 waves (4 x 2), single buffer / double-buffered (BM = 128)
+//   4 / 5   gather_gemm_bf16s_ws_kernel: wave-specialised, 4 producer + 8 / 4 consumer waves, 2 tiles in flight (4: not 64 x 64)
+//   6 / 7   as 4 / 5 with 3 tiles in flight
+//   8       gather_halo_bf16s_kernel: the halo-image kernel, 8 waves, 128-row tiles; images of 160 / 264 rows; 2 or 3 pieces; up2
+//   9       the same on 256-row tiles (8 waves of 64 x 64): half the weight-piece bytes per FLOP through the vector-memory path, pays
+//           once the problem has >= 2 x 256 such row tiles; images of 320 / 528 rows (3 pieces and 528 rows: 64 columns only;
+//           up2: 320 rows only -- 6-tap convs on 256-row tiles need 298)
+//   10 / 11 gather_halo_ws_bf16s_kernel: wave-specialised halo kernel (8 consumer + 2 producer waves), 128- / 256-row tiles, where
+//           two image buffers + two weight stages fit the 160 KiB of LDS: images of 160 / 264 rows; 264 / 320 (320: 2 pieces)
+//   12 / 13 the same with three weight-tile buffers (the producers request two stages ahead): 3 pieces on 64 columns only;
+//           images of 160 / 264 rows; 264 rows
+//   14 / 15 FOUR consumer waves with 128 x 64 wave tiles (one per SIMD) + 2 producers on the 256 x 128 tile: 25 % fewer LDS
+//           fragment bytes per MFMA; compiler-scheduled / pinned (sched_barrier) pipeline; 2 pieces; images of 264 / 320 rows
+//   16 / 17 gather_halo_ws4_bf16s_kernel: 8 consumer + 4 DMA-only loader waves, 256-row tiles, with / without the quarter-stage
+//           stagger of the consumers' second half; 2 pieces; images of 264 / 320 rows beside a raw ring of 3 x 88 / 3 x 64 rows
+//   18      as 16 on v_mfma_f32_16x16x32 (gather_halo_ws4m_bf16s_kernel)
+//   19      the 8-wave halo kernel on 256 x 160 tiles, 8 x 1 waves of 32 x 160 (19128128: the fields are placeholders).  For the
+//           output conv (141 -> 144 channels): ONE column tile instead of three 64-wide ones -- 10 % instead of 25 % of the matrix
+//           work on padding columns, the image of a channel block staged once instead of three times.  2 pieces; 320 / 528 rows
+//   29      the 8-wave halo kernel on 256 x 256 tiles, 4 x 2 waves of 64 x 128 (29128128: placeholders): a quarter fewer operand
+//           bytes per multiply through the CU's fetch path than 256 x 128.  2 pieces; images of <= 320 rows; up2
+// "2 pieces" includes the two fp16 pieces (SVAE_PIECES_F16X2).  Variants 9, 11 and 13 .. 19 carry 128 in the row field of their
+// code and run 256-row tiles; V >= 20 other than 29 are the diagnostic variants of the ablation build (256-row tiles).
+struct SplitGeo {
+  int v;               // kernel variant
+  int bm, bn;          // workgroup tile really used
+  int code_bm;         // row field of the code
+  int blocks_m[2];     // row tiles per phase
+  unsigned grid_x, grid_y;
+  int rows;            // halo variants: upper bound of the image rows over all tiles of both phases, else 0
+  int rmax;            // halo variants: image rows the kernel instance is built with, else 0
+  int status;          // SVAE_OK, or SVAE_ERR_SHAPE: this variant does not exist for the code's tile / pieces / image rows --
+  const char* why;     // -- with this message, a format that takes why_arg
+  int why_arg;
+};
+
+// pieces: of the launch (the tile does not depend on it: the introspection calls pass 2, which every variant is built for)
+inline SplitGeo split_gather_geometry(const GatherArgs& g, int code, int pieces) {
+  SplitGeo s = {};
+  Tile t;
+  if (!decode_tile(code, t)) { t = pick_tile(g.M[0], g.M[1], g.N); t.dma = 1; if (g.up) { t.bm = 128; t.dma = 8; } }
+  const int v = s.v = t.dma;
+  const bool rows256 = v == 9 || v == 11 || v >= 13;
+  s.code_bm = t.bm;
+  s.bm = rows256 ? 256 : t.bm;
+  s.bn = v == 19 ? 160 : (v == 29 ? 256 : t.bn);
+  for (int p = 0; p < 2; ++p) s.blocks_m[p] = (int)((g.M[p] + s.bm - 1) / s.bm);
+  s.grid_x = (unsigned)(s.blocks_m[0] + s.blocks_m[1]);
+  s.grid_y = (unsigned)((g.N + s.bn - 1) / s.bn);
+  int r0 = 0, r1 = 0;  // the image rows the variant's kernels are built with
+  switch (v) {
+    case 8: case 10: case 12: r0 = 160; r1 = 264; break;
+    case 9: case 19: r0 = 320; r1 = 528; break;
+    case 11: case 14: case 15: case 16: case 17: case 18: r0 = 264; r1 = 320; break;
+    case 13: r0 = r1 = 264; break;
+    case 29: r0 = r1 = 320; break;
+    default: break;
+  }
+  if (r0) {
+    s.rows = halo_rows(g, rows256 ? 256 : 128);
+    s.rmax = s.rows <= r0 ? r0 : r1;
+  }
+
+  // does the combination exist?
+  auto refuse = [&s](const char* why, int arg) { s.status = SVAE_ERR_SHAPE; s.why = why; s.why_arg = arg; return s; };
+  static const char* const unsupported = "split gather: tile code %d unsupported";
+  static const char* const not_affine = "split gather: tap tables are not arithmetic progressions";
+  const bool two = pieces == 2 || pieces == SVAE_PIECES_F16X2, two_three = two || pieces == 3;
+  const int rows = s.rows;
+  if (g.up && v != 8 && v != 9 && v != 29)
+    return refuse("split gather: the fused x2 upsample of the input exists in the halo kernels (tile codes 8 / 9 / 29), not in code %d", code);
+  switch (v) {
+    case 0: case 1: case 5: case 7: break;
+    case 2: case 3:
+      if (t.bm != 128) return refuse(unsupported, code);
+      break;
+    case 4: case 6:
+      if (t.bm != 128 && t.bn != 128) return refuse(unsupported, code);
+      break;
+    case 8:
+      if (t.bm != 128) return refuse(unsupported, code);
+      if (!two_three) return refuse("split gather: the halo kernel is built for 2 or 3 pieces", 0);
+      if (rows > 264) return refuse("split gather: halo image of %d rows does not fit", rows);
+      break;
+    case 9:
+      if (t.bm != 128) return refuse(unsupported, code);
+      if (!two_three) return refuse("split gather: the halo kernel is built for 2 or 3 pieces", 0);
+      if (rows > 528 || (pieces == 3 && rows > 320 && t.bn > 64)) return refuse("split gather: 256-row halo image of %d rows does not fit", rows);
+      if (g.up && rows > 320) return refuse("split gather: the fused upsample exists for 256-row halo images of <= 320 rows (%d)", rows);
+      break;
+    case 10: case 11:
+      if (t.bm != 128) return refuse(unsupported, code);
+      if (!plan_is_affine(g)) return refuse(not_affine, 0);
+      if (!two_three) return refuse("split gather: the halo kernels are built for 2 or 3 pieces", 0);
+      if (v == 10 && rows > 264) return refuse("split gather: halo image of %d rows does not fit", rows);
+      if (v == 11 && (rows > 320 || (rows > 264 && pieces == 3))) return refuse("split gather: 256-row halo image of %d rows does not fit twice", rows);
+      break;
+    case 12: case 13:
+      if (t.bm != 128) return refuse(unsupported, code);
+      if (!plan_is_affine(g)) return refuse(not_affine, 0);
+      if (!two_three) return refuse("split gather: the halo kernels are built for 2 or 3 pieces", 0);
+      if (pieces == 3 && t.bn != 64) return refuse("split gather: three weight buffers with 3 pieces exist for 64-column tiles only", 0);
+      if (rows > 264) return refuse("split gather: halo image of %d rows does not fit", rows);
+      break;
+    case 14: case 15:
+      if (t.bm != 128 || t.bn != 128) return refuse(unsupported, code);
+      if (!plan_is_affine(g)) return refuse(not_affine, 0);
+      if (!two) return refuse("split gather: the 128 x 64 wave tiles are built for 2 pieces", 0);
+      if (rows > 320) return refuse("split gather: 256-row halo image of %d rows does not fit", rows);
+      break;
+    case 16: case 17: case 18:
+      if (t.bm != 128) return refuse(unsupported, code);
+      if (!plan_is_affine(g)) return refuse(not_affine, 0);
+      if (!two) return refuse("split gather: the 12-wave halo kernel is built for 2 pieces", 0);
+      if (rows > 320 || ws4_slice_rows(g, s.rmax) > (s.rmax == 264 ? 88 : 64))
+        return refuse("split gather: 256-row halo image of %d rows / its raw slices do not fit", rows);
+      break;
+    case 19:
+      if (t.bm != 128 || t.bn != 128) return refuse(unsupported, code);
+      if (!two) return refuse("split gather: the 256 x 160 halo tile is built for 2 pieces", 0);
+      if (rows > 528) return refuse("split gather: 256-row halo image of %d rows does not fit", rows);
+      break;
+    case 29:
+      if (t.bm != 128 || t.bn != 128) return refuse(unsupported, code);
+      if (!two) return refuse("split gather: the 256 x 256 halo tile is built for 2 pieces", 0);
+      if (rows > 320) return refuse("split gather: 256 x 256 halo tile: image of %d rows does not fit", rows);
+      break;
+    default: return refuse(unsupported, code);
+  }
+  return s;
+}
+
+// what a launcher answers when it has no instance for a geometry the resolver let through (they must agree: not reached)
+inline int split_no_instance(const SplitGeo& s, int pieces) {
+  set_error("split gather: no kernel instance of variant %d for a %d x %d tile, %d pieces, %d image rows", s.v, s.bm, s.bn, pieces, s.rmax);
+  return SVAE_ERR_SHAPE;
+}
+
+// wave-specialised halo kernels (halo_ws_bf16s.hip): variants 10 .. 18 of a geometry that exists
+int launch_split_halo_ws(const SplitGatherArgs& sa, const SplitGeo& geo, dim3 grid, hipStream_t st, int pieces);
+#ifdef SVAE_ABLATION_KERNELS
+// the diagnostic variants (V >= 20 other than 29; g.blocks_m set): true when the launch was one of theirs, its status in *e
+bool launch_split_halo_diag(const SplitGatherArgs& sa, const SplitGeo& geo, hipStream_t st, int pieces, int* e);
+#endif
 
 }  // namespace svae

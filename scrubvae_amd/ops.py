@@ -200,10 +200,7 @@ def split_weights_batched(users):
         chunk = todo[i: i + _lib.MAX_SPLIT_TASKS]
         arr = (_lib.SplitTask * len(chunk))()
         for t, (cv, w) in zip(arr, chunk):
-            if cv._wsplit is None:
-                n = int(_lib.lib().svae_conv_split_bytes(C.byref(cv.desc)))
-                cv._wsplit = torch.empty(n + 64, dtype=torch.uint8, device=w.device)
-            t.w, t.wsplit, t.kernel, t.c_in, t.c_out = w.data_ptr(), cv._wsplit.data_ptr(), cv.kernel, cv.c_in_p, cv.c_out_p
+            t.w, t.wsplit, t.kernel, t.c_in, t.c_out = w.data_ptr(), cv._split_buffer(w).data_ptr(), cv.kernel, cv.c_in_p, cv.c_out_p
         check(_lib.lib().svae_conv_split_weights_batched(arr, len(chunk), _stream()), "conv_split_weights_batched")
         for cv, w in chunk:
             cv._split_epoch, cv._split_src = WEIGHT_EPOCH, w.data_ptr()
@@ -274,13 +271,17 @@ class Conv:
         self.desc.up2 = 1 if (self.up2 and (kind == "fwd" or (kind == "wgrad" and self.up2_wgrad))) else 0
         return C.byref(self.desc)
 
+    def _split_buffer(self, w):
+        """Where the piece planes of `w` live (allocated at first use)."""
+        if self._wsplit is None:
+            n = int(_lib.lib().svae_conv_split_bytes(C.byref(self.desc)))
+            self._wsplit = torch.empty(n + 64, dtype=torch.uint8, device=w.device)
+        return self._wsplit
+
     def split_weights(self, w):
         """bf16 piece planes of `w` for the split kernels; re-split once per weight epoch."""
         if self._split_epoch != WEIGHT_EPOCH or self._split_src != w.data_ptr():
-            if self._wsplit is None:
-                n = int(_lib.lib().svae_conv_split_bytes(C.byref(self.desc)))
-                self._wsplit = torch.empty(n + 64, dtype=torch.uint8, device=w.device)
-            check(_lib.lib().svae_conv_split_weights(C.byref(self.desc), _p(w), _p(self._wsplit), _stream()), "conv_split_weights")
+            check(_lib.lib().svae_conv_split_weights(C.byref(self.desc), _p(w), _p(self._split_buffer(w)), _stream()), "conv_split_weights")
             self._split_epoch, self._split_src = WEIGHT_EPOCH, w.data_ptr()
         return self._wsplit
 
@@ -526,12 +527,7 @@ class Conv:
             sdw = torch.empty(self.kernel * self.c_in_p * self.c_out_p + 16, device=x.device)
             sdb = torch.empty(self.c_out_p, device=x.device)
             self.desc.tile[2] = 0
-            need = 0
-            for code in (_SPLIT_WGRAD_CODES if self._base_pieces("wgrad") else _WGRAD_CODES):  # scratch workspace large enough for every candidate
-                self.desc.tile[2] = code
-                need = max(need, int(_lib.lib().svae_conv_wgrad_workspace(self._dref("wgrad"))))
-            self.desc.tile[2] = 0
-            sws = torch.empty(need // 4 + 16, device=x.device)
+            sws = torch.empty(self.wgrad_workspace_bytes() // 4 + 16, device=x.device)  # scratch workspace large enough for every candidate
             self._tune("wgrad", lambda: self._launch_wgrad(x, dy, sdw, sdb, sws, 0))
             if ws.numel() * ws.element_size() < self.wgrad_workspace_bytes():
                 raise RuntimeError("conv_wgrad: workspace smaller than the tuned tile needs; size it with "
