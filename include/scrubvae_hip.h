@@ -721,6 +721,42 @@ int svae_silhouette_medoids(const double* a, const int* lab, int n, int K, unsig
 long long svae_knn_work(int n, int k);
 int svae_knn(const double* Z, int ld, int d, int n, int k, const int* group, void* work, int* idx, double* dist, void* stream);
 
+/* ------------------------------------------------------- t-SNE of the latents on their exact kNN graph (csrc/tsne.hip) --------- */
+/* sklearn's TSNE with an exact gradient, all fp64, no FMA contraction, every result bit-reproducible for a given (n, chunks).
+ *
+ * svae_tsne_search: the perplexity search of sklearn's _binary_search_perplexity on d2 [n][k], the squared distances to each
+ * row's k neighbours (1 <= k <= SVAE_KNN_MAX_K, n >= 1): beta = 1, bounds -inf / +inf, at most SVAE_TSNE_SEARCH_STEPS steps of
+ * sum = sum_j exp(-d2 beta) (a zero sum becomes 1e-8), H = log(sum) + beta * sum_j(d2 exp(-d2 beta)) / sum, both sums in
+ * neighbour order, until |H - log(perplexity)| <= 1e-5; H too large doubles beta (or takes the midpoint with the upper bound
+ * once there is one), H too small halves it (or the midpoint with the lower bound).  P [n][k] = exp(-d2 beta) / sum at the last
+ * beta evaluated; beta [n] is the search variable as the loop leaves it (after 100 steps without convergence: one update past
+ * the beta of P, as sklearn's). */
+#define SVAE_TSNE_SEARCH_STEPS 100
+int svae_tsne_search(const double* d2, int k, int n, double perplexity, double* P, double* beta, void* stream);
+/* svae_tsne_repulsion: for every row i of Y [n][2] (2 <= n <= 2^26), over all j != i (the row left out by index) with
+ * d = y_i - y_j and q = 1.0 / (1.0 + (d0 d0 + d1 d1)) (the division correctly rounded):
+ *     R [n][2] = sum_j q q d        rowq [n] = sum_j q        Z [1] = sum_i rowq[i]
+ * The full square, so every row's sums have one owner: a block of 256 threads keeps one row per thread in registers and streams
+ * the candidates from LDS in ascending j.  The columns are split into `chunks` ranges of whole 64-column tiles (grid y);
+ * 1 <= chunks <= SVAE_TSNE_MAX_CHUNKS is taken as given (at most one per tile), chunks = 0 picks min(8, tiles) and fewer once
+ * the grid holds 512 blocks (the silhouette's rule).  The chunk partials are added in chunk order; Z is reduced at fixed
+ * positions (thread t of 256 adds rowq[t], rowq[t + 256], ... compensated, then a fixed tree).  work: svae_tsne_repulsion_work
+ * doubles (0 for arguments out of range): chunks x 3 x rows padded to 256. */
+#define SVAE_TSNE_MAX_CHUNKS 8
+long long svae_tsne_repulsion_work(int n, int chunks);
+int svae_tsne_repulsion(const double* Y, int n, int chunks, double* work, double* R, double* rowq, double* Z, void* stream);
+/* svae_tsne_step: one descent step on the CSR joint probabilities (rowptr [n + 1] int32, col int32, val fp64; p = exag * val).
+ * Per row, over its entries in stored order with d = y_i - y_j, w = 1.0 + (d0 d0 + d1 d1):
+ *     A_i = sum val (1.0 / w) d        klpart[i] = sum p log(p w)        grad_i = 4.0 (exag A_i - R_i / Z)
+ *     gains = update grad < 0 ? gains + 0.2 : gains 0.8, at least 0.01;   grad = grad gains   (sklearn's order)
+ *     update = momentum update - lr grad;   gradsq[i] = grad . grad (of the gained gradient: what sklearn's norm is taken of)
+ * (an entry with p = 0 adds nothing to klpart) and, in a second launch so that no row sees a neighbour's new position, Y = Y + update.  klpart and gradsq may both be NULL
+ * (no check this iteration).  update == NULL evaluates only: klpart and gradsq (of the plain gradient) at Y, nothing modified. */
+int svae_tsne_step(const int* rowptr, const int* col, const double* val, double exag, double* Y, const double* R, const double* Z,
+                   double* update, double* gains, double momentum, double lr, int n, double* klpart, double* gradsq, void* stream);
+/* out[0] = sum of a [n], out[1] = sum of b [n] (b nullable): compensated sums at fixed positions, then a fixed tree */
+int svae_tsne_sums(const double* a, const double* b, long long n, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

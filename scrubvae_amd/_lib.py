@@ -205,6 +205,11 @@ SIGNATURES = {
     "svae_silhouette_medoids": (I, [P, P, I, I, P, P, P]),
     "svae_knn_work": (LL, [I, I]),
     "svae_knn": (I, [P, I, I, I, I, P, P, P, P, P]),
+    "svae_tsne_search": (I, [P, I, I, D, P, P, P]),
+    "svae_tsne_repulsion_work": (LL, [I, I]),
+    "svae_tsne_repulsion": (I, [P, I, I, P, P, P, P, P]),
+    "svae_tsne_step": (I, [P, P, P, D, P, P, P, P, P, D, D, I, P, P, P]),
+    "svae_tsne_sums": (I, [P, P, LL, P, P]),
 }
 
 _lib = None
@@ -242,6 +247,7 @@ MMD_WORK_WORDS = 8256  # include/scrubvae_hip.h SVAE_MMD_WORK_WORDS
 MMD_NULL_MAX = 65536  # include/scrubvae_hip.h SVAE_MMD_NULL_MAX
 SIL_MAX_CLUSTERS = 4096  # include/scrubvae_hip.h SVAE_SIL_MAX_CLUSTERS
 KNN_MAX_K = 90  # include/scrubvae_hip.h SVAE_KNN_MAX_K
+TSNE_SEARCH_STEPS, TSNE_MAX_CHUNKS = 100, 8  # include/scrubvae_hip.h SVAE_TSNE_*
 MAX_LOSS_TERMS = 48  # include/scrubvae_hip.h SVAE_MAX_LOSS_TERMS
 ERR_SHAPE, ERR_ALIGN, ERR_WORKSPACE, ERR_LAUNCH, ERR_ARG = -1, -2, -3, -4, -5  # include/scrubvae_hip.h svae_status
 

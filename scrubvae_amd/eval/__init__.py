@@ -1,4 +1,5 @@
 from .cluster import GaussianMixture, dbscan, gmm  # noqa: F401
+from .embed import TSNE, tsne, tsne_affinities  # noqa: F401
 from .eval import generative_restrictiveness  # noqa: F401
 from .hdbscan import HDBSCAN  # noqa: F401
 from .metrics import (cluster_entropy, hungarian_match, knn_class_rand_cv, knn_reg_rand_cv, lda_rand_cv, linear_rand_cv,  # noqa: F401
