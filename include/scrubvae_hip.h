@@ -757,6 +757,36 @@ int svae_tsne_step(const int* rowptr, const int* col, const double* val, double 
 /* out[0] = sum of a [n], out[1] = sum of b [n] (b nullable): compensated sums at fixed positions, then a fixed tree */
 int svae_tsne_sums(const double* a, const double* b, long long n, double* out, void* stream);
 
+/* ------------------------------------------------------- Independence of latents and a variable: HSIC (csrc/hsic.hip) ---------- */
+/* The Hilbert-Schmidt independence criterion with a permutation null, fp64, nothing of size n^2 stored, every result
+ * bit-reproducible.  Z [n][ld] fp64 rows, not centred, 2 <= n < 2^26; K_ij = exp((-s_ij) / hz) with s the squared distance of
+ * csrc/pair_tiles.h (feature order, no FMA, no sqrt round trip).  The variable is either Y [n][q] fp64 rows, contiguous,
+ * 1 <= q <= SVAE_HSIC_MAX_Y, with L_ij = exp((-t_ij) / hy) built the same way, or lab [n] int32 with L_ij = [lab_i == lab_j].
+ * Bandwidths are device pointers (hm + 1 of svae_mmd_select on the rows alone, or a given value).  A permutation table perm
+ * [P][n] int32 holds one permutation of 0..n-1 per row (the caller guarantees that): under row p, y_perm[p][i] is paired with z_i.
+ * A null perm with P = 1 is the identity.  1 <= P <= SVAE_MMD_NULL_MAX per call.
+ *
+ * svae_hsic_moments: of one kernel matrix M (X [n][ld] with bandwidth h, or lab; exactly one of X and lab is non-null), over the
+ * full square with the diagonal: rowsum [n] = sum_j M_ij, mom = {sum_ij M_ij, sum_ij M_ij^2, sum_i rowsum_i^2}.  One all-pairs
+ * pass, per-block partials at fixed positions in work, compensated fixed-order reductions.
+ * svae_hsic_cross: out[p] = A_p = sum_{i<j} K_ij L_perm[p][i] perm[p][j].  A block of 256 threads holds a 64 x 64 tile of K in
+ * registers and regenerates L for the same pairs for each of the SVAE_HSIC_PERMS permutations of its chunk from the permuted
+ * rows of y staged in LDS; K is recomputed once per chunk.  Fixed order throughout (pairs of a tile, tiles in column order, a
+ * fixed cross-lane tree, waves in order, per-block partials in work, a compensated reduction), no floating-point atomics: out[p]
+ * depends on row p of perm alone, not on its position, on P or on the call it falls in.
+ * svae_hsic_dots: out[p] = sum_i (k_i - t) (l_perm[p][i] - t), t = 1 when tilde is non-zero (the unbiased estimator's row sums
+ * without the diagonal) and 0 otherwise; a gather and a compensated fixed-order sum per permutation. */
+#define SVAE_HSIC_MAX_Y 4
+#define SVAE_HSIC_PERMS 16
+/* doubles of work that svae_hsic_moments and svae_hsic_cross need at n rows and P permutations per call (0 for n < 2, n >= 2^26
+ * or a P out of range): column chunks (at most 8) x row tiles x the larger of 128 and P padded to SVAE_HSIC_PERMS */
+long long svae_hsic_work(int n, int P);
+int svae_hsic_moments(const double* X, int ld, int d, const int* lab, int n, const double* h, double* work, double* rowsum,
+                      double* mom, void* stream);
+int svae_hsic_cross(const double* Z, int ld, int d, int n, const double* hz, const double* Y, int q, const int* lab,
+                    const double* hy, const int* perm, int P, double* work, double* out, void* stream);
+int svae_hsic_dots(const double* k, const double* l, int n, const int* perm, int P, int tilde, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -210,6 +210,10 @@ SIGNATURES = {
     "svae_tsne_repulsion": (I, [P, I, I, P, P, P, P, P]),
     "svae_tsne_step": (I, [P, P, P, D, P, P, P, P, P, D, D, I, P, P, P]),
     "svae_tsne_sums": (I, [P, P, LL, P, P]),
+    "svae_hsic_work": (LL, [I, I]),
+    "svae_hsic_moments": (I, [P, I, I, P, I, P, P, P, P, P]),
+    "svae_hsic_cross": (I, [P, I, I, I, P, P, I, P, P, P, I, P, P, P]),
+    "svae_hsic_dots": (I, [P, P, I, P, I, I, P, P]),
 }
 
 _lib = None
@@ -248,6 +252,7 @@ MMD_NULL_MAX = 65536  # include/scrubvae_hip.h SVAE_MMD_NULL_MAX
 SIL_MAX_CLUSTERS = 4096  # include/scrubvae_hip.h SVAE_SIL_MAX_CLUSTERS
 KNN_MAX_K = 90  # include/scrubvae_hip.h SVAE_KNN_MAX_K
 TSNE_SEARCH_STEPS, TSNE_MAX_CHUNKS = 100, 8  # include/scrubvae_hip.h SVAE_TSNE_*
+HSIC_MAX_Y, HSIC_PERMS = 4, 16  # include/scrubvae_hip.h SVAE_HSIC_*
 MAX_LOSS_TERMS = 48  # include/scrubvae_hip.h SVAE_MAX_LOSS_TERMS
 ERR_SHAPE, ERR_ALIGN, ERR_WORKSPACE, ERR_LAUNCH, ERR_ARG = -1, -2, -3, -4, -5  # include/scrubvae_hip.h svae_status
 

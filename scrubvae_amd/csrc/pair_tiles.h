@@ -1,5 +1,5 @@
 // All-pairs squared distances of fp64 rows in 64 x 64 tiles, the shared layer of hdbscan.hip, mmd.hip, mmd_null.hip,
-// silhouette.hip and knn.hip: a block of 256 threads holds 64 rows (lane = row, the same rows in each of the 4 waves) against 64 candidates
+// silhouette.hip, knn.hip and hsic.hip: a block of 256 threads holds 64 rows (lane = row, the same rows in each of the 4 waves) against 64 candidates
 // (wave w takes candidates [16 w, 16 w + 16)), both staged through LDS 16 features at a time.
 // s = ((x0 - y0)^2 + (x1 - y1)^2) + ... in feature order, every subtract, multiply and add rounded on its own: the pragma below
 // is part of the contract.  A kernel builds its block's rows once (pair_rows) and asks for one tile of s at a time (pair_tile).

@@ -2,6 +2,7 @@ from .cluster import GaussianMixture, dbscan, gmm  # noqa: F401
 from .embed import TSNE, tsne, tsne_affinities  # noqa: F401
 from .eval import generative_restrictiveness  # noqa: F401
 from .hdbscan import HDBSCAN  # noqa: F401
+from .independence import HSICPermutationResult, hsic, hsic_bandwidth, hsic_permutation_test  # noqa: F401
 from .metrics import (cluster_entropy, hungarian_match, knn_class_rand_cv, knn_reg_rand_cv, lda_rand_cv, linear_rand_cv,  # noqa: F401
                       log_class_rand_cv, mlp_rand_cv, mmd_bandwidth, mmd_estimate, mmd_permutation_test, mmd_permutations,
                       qda_rand_cv, shannon_entropy)
