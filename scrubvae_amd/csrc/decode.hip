@@ -10,6 +10,8 @@
 // group.  Every reduction walks its rows in one fixed order (no atomics on floating point): results are bit-reproducible.
 #include "svae_internal.h"
 
+#include "fixed_sum.h"  // block_sum_all; sets no contraction pragma
+
 namespace svae {
 
 constexpr int CV_LDS_MAX = 152 * 1024;  // dynamic LDS ceiling: 160 KiB less the kernels' static arrays (<= 5 KiB)
@@ -23,19 +25,6 @@ __device__ __forceinline__ double sigmoid_d(double t) {
   return e / (1.0 + e);
 }
 
-// fixed-shape tree sum over a 256-thread block; result valid in every thread
-__device__ __forceinline__ double block_sum_d256(double v, double* red) {
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
-}
-
 // ---- column means: one block per column, thread t sums rows t, t + 256, ... in order, then a fixed tree
 __global__ __launch_bounds__(256) void cv_colmean_kernel(const float* __restrict__ x, int ldx, int d, const float* __restrict__ y,
                                                          int ldy, int n, double* __restrict__ mean) {
@@ -45,7 +34,7 @@ __global__ __launch_bounds__(256) void cv_colmean_kernel(const float* __restrict
   const int ld = c < d ? ldx : ldy;
   double s = 0.0;
   for (int r = threadIdx.x; r < n; r += 256) s += (double)src[(long long)r * ld];
-  s = block_sum_d256(s, red);
+  s = block_sum_all<256>(s, red);
   if (threadIdx.x == 0) mean[c] = s / (double)n;
 }
 
@@ -212,9 +201,9 @@ __global__ __launch_bounds__(256) void cv_r2_kernel(const double* __restrict__ A
     sy += yc;
     syy = fma(yc, yc, syy);
   }
-  sr = block_sum_d256(sr, red);
-  sy = block_sum_d256(sy, red);
-  syy = block_sum_d256(syy, red);
+  sr = block_sum_all<256>(sr, red);
+  sy = block_sum_all<256>(sy, red);
+  syy = block_sum_all<256>(syy, red);
   if (threadIdx.x == 0) {
     double* s = stats + ((long long)f * ny + o) * 4;
     s[0] = sr; s[1] = sy; s[2] = syy; s[3] = (double)(hi[f] - lo[f]);
@@ -302,7 +291,7 @@ __global__ __launch_bounds__(256) void logreg_stats_kernel(const LogregProb pb, 
   cf[threadIdx.x] = coef;
   const int chunks = gridDim.x;
   double* pp = part + ((long long)p * chunks + blockIdx.x) * (D + 1);
-  const double ls = block_sum_d256(loss, red);  // also orders the cf writes before the reads below
+  const double ls = block_sum_all<256>(loss, red);  // also orders the cf writes before the reads below
   if (threadIdx.x == 0) pp[D] = ls;
   const int r0 = blockIdx.x * LR_ROWS, nr = min(LR_ROWS, pb.n - r0);
   for (int j = threadIdx.x; j < D; j += 256) {
@@ -437,7 +426,7 @@ __global__ __launch_bounds__(256) void logreg_ls_kernel(const LogregProb pb, Log
   double t = 1.0;
   for (int k = 0; k < LS_STEPS; ++k, t *= 0.5) {
     const double l = ok ? Cc * softplus_d(-s * (u + t * du)) : 0.0;
-    const double sum = block_sum_d256(l, red);
+    const double sum = block_sum_all<256>(l, red);
     if (threadIdx.x == 0) part[((long long)p * gridDim.x + blockIdx.x) * LS_STEPS + k] = sum;
   }
 }

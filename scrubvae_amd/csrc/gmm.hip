@@ -6,6 +6,8 @@
 // the same host random draws give bit-identical results on one device.
 #include "svae_internal.h"
 
+#include "fixed_sum.h"  // block_sum_all; sets no contraction pragma: the fma below stay
+
 namespace svae {
 
 constexpr int KPP_ROWS = 256;   // rows per block of the k-means++ distance kernel = one chunk of its prefix sum
@@ -15,18 +17,6 @@ constexpr int ES_J = 8;         // E-step (full): output columns of (x - mu) P p
 constexpr int MS_ROWS = 64;     // M-step: rows staged per step
 constexpr int GT = 32;          // M-step (full): edge of one output tile of the weighted Gram matrix
 constexpr int CHUNK_ROWS = 4096;  // M-step row chunk per output tile (see svae_gmm_chunks)
-
-__device__ __forceinline__ double gmm_block_sum(double v, double* red) {  // fixed-shape tree over 256 threads, valid in every thread
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
-}
 
 // ---- k-means++ -----------------------------------------------------------------------------------------------------------------
 // d2[t][r] = min(closest[r], sum_j (A[r][j] - A[cand[t]][j])^2) (closest NULL: no minimum), part[t][b] = tree sum of d2[t] over
@@ -50,7 +40,7 @@ __global__ __launch_bounds__(256) void gmm_kpp_dist_kernel(const double* __restr
       s = fmin(cl, s);
       d2[(long long)t * n + r] = s;
     }
-    const double bs = gmm_block_sum(s, red);
+    const double bs = block_sum_all<256>(s, red);
     if (threadIdx.x == 0) part[(long long)t * gridDim.x + blockIdx.x] = bs;
   }
 }
@@ -193,7 +183,7 @@ __global__ __launch_bounds__(256) void gmm_sum_kernel(const double* __restrict__
   __shared__ double red[256];
   double s = 0.0;
   for (int i = threadIdx.x; i < m; i += 256) s += x[i];
-  s = gmm_block_sum(s, red);
+  s = block_sum_all<256>(s, red);
   if (threadIdx.x == 0) out[0] = s / div;
 }
 

@@ -13,15 +13,16 @@
 // of its chunk regenerates L for the same 16 pairs from the permuted rows of y staged in LDS: the row's y_pi(i) per lane, the 16
 // candidates' y_pi(j) read wave-uniformly as a broadcast.  K is recomputed once per chunk of HPC permutations.
 // Fixed order: the 16 pairs of a lane within a tile, the tile's sum added to the permutation's accumulator in column order of the
-// tiles, a fixed cross-lane tree, the four waves in order, per-block partials at fixed positions, a compensated fixed-order
-// reduction.  No floating-point atomics.  out[p] depends on row p of the permutation table alone: every slot of a chunk runs the
-// same instructions on its own operands.
+// tiles, a fixed cross-lane tree, then the orders of fixed_sum.h: the four waves in order, per-block partials at fixed positions,
+// compensated strided sums and the block tree.  No floating-point atomics.  out[p] depends on row p of the permutation table
+// alone: every slot of a chunk runs the same instructions on its own operands.
 #include "svae_internal.h"
 
 #include <algorithm>
 #include <type_traits>
 
 #include "pair_tiles.h"   // the tile walk and #pragma clang fp contract(off)
+#include "fixed_sum.h"    // the closing sums
 #include "hsic_common.h"  // hsic_value, hsic_delta
 
 namespace svae {
@@ -99,8 +100,7 @@ __global__ __launch_bounds__(256) void hsic_moments_kernel(const double* __restr
   __syncthreads();
   if (threadIdx.x < 128) {  // the four waves of a row in order
     const int k = threadIdx.x >> 6;
-    const double* r = red + k * 256 + lane;
-    part[((long long)k * gridDim.y + blockIdx.y) * npad + r0 + lane] = ((r[0] + r[64]) + r[128]) + r[192];
+    part[((long long)k * gridDim.y + blockIdx.y) * npad + r0 + lane] = waves4(red + k * 256 + lane, 64);
   }
 }
 
@@ -109,35 +109,29 @@ __global__ __launch_bounds__(256) void hsic_rows_kernel(double* __restrict__ par
                                                         double* __restrict__ rowsum) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  double sum[2] = {0.0, 0.0}, comp[2] = {0.0, 0.0};
+  NeumaierSums<2> acc;
   for (int y = 0; y < gy; ++y) {
 #pragma unroll
-    for (int k = 0; k < 2; ++k) neumaier_add(sum[k], comp[k], part[((long long)k * gy + y) * npad + i]);
+    for (int k = 0; k < 2; ++k) acc.add(k, part[((long long)k * gy + y) * npad + i]);
   }
-  rowsum[i] = sum[0] + comp[0];
-  part[(long long)gy * npad + i] = sum[1] + comp[1];  // read above by this thread alone
+  rowsum[i] = acc.total(0);
+  part[(long long)gy * npad + i] = acc.total(1);  // read above by this thread alone
 }
 
-// One block: mom = {sum_i k_i, sum_i (row i's sum of squares), sum_i k_i^2}, compensated per thread, then a fixed tree
+// One block: mom = {sum_i k_i, sum_i (row i's sum of squares), sum_i k_i^2}, compensated per thread, then the block tree
 __global__ __launch_bounds__(1024) void hsic_totals_kernel(const double* __restrict__ rowsum, const double* __restrict__ sq, int n,
                                                            double* __restrict__ mom) {
   __shared__ double red[3 * 1024];
-  double sum[3] = {0.0, 0.0, 0.0}, comp[3] = {0.0, 0.0, 0.0};
+  NeumaierSums<3> acc;
   for (int i = threadIdx.x; i < n; i += 1024) {
     const double k = rowsum[i];
-    neumaier_add(sum[0], comp[0], k);
-    neumaier_add(sum[1], comp[1], sq[i]);
-    neumaier_add(sum[2], comp[2], k * k);
+    acc.add(0, k);
+    acc.add(1, sq[i]);
+    acc.add(2, k * k);
   }
 #pragma unroll
-  for (int k = 0; k < 3; ++k) red[k * 1024 + threadIdx.x] = sum[k] + comp[k];
-  __syncthreads();
-  for (int o = 512; o > 0; o >>= 1) {
-    if (threadIdx.x < o)
-#pragma unroll
-      for (int k = 0; k < 3; ++k) red[k * 1024 + threadIdx.x] = red[k * 1024 + threadIdx.x] + red[k * 1024 + threadIdx.x + o];
-    __syncthreads();
-  }
+  for (int k = 0; k < 3; ++k) red[k * 1024 + threadIdx.x] = acc.total(k);
+  block_tree<1024, 3>(red);
   if (threadIdx.x < 3) mom[threadIdx.x] = red[threadIdx.x * 1024];
 }
 
@@ -241,56 +235,45 @@ __global__ __launch_bounds__(256) void hsic_cross_kernel(const double* __restric
   }
 #pragma unroll
   for (int p = 0; p < HPC; ++p) {
-    double v = acc[p];
+    double v = acc[p];  // wave_sum_d's butterfly, written out: the call moves the registers of the whole kernel
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o, 64);  // a + b == b + a: the same bits in every lane
     if (lane == 0) red[wave * HPC + p] = v;
   }
   __syncthreads();
-  if (threadIdx.x < HPC) {
-    const double* r = red + threadIdx.x;
-    out[threadIdx.x] = ((r[0] + r[HPC]) + r[2 * HPC]) + r[3 * HPC];
-  }
+  if (threadIdx.x < HPC) out[threadIdx.x] = waves4(red + threadIdx.x, HPC);
 }
 
 // Block b: permutations [16 b, 16 b + 16).  Thread (column c = t & 15, slot s = t >> 4) adds the partials of blocks s, s + 16, ...
-// with a compensated (Neumaier) sum, then a fixed tree over the 16 slots.
+// with a compensated sum, then the block tree stopped at the 16 columns (fixed_sum.h).
 __global__ __launch_bounds__(256) void hsic_cross_reduce_kernel(const double* __restrict__ part, long long blocks, int ppad, int P,
                                                                 double* __restrict__ out) {
   __shared__ double red[256];
   const int slot = threadIdx.x >> 4;
   const int p = (int)blockIdx.x * 16 + (threadIdx.x & 15);
-  double sum = 0.0, comp = 0.0;
+  NeumaierSums<1> acc;
   if (p < ppad)
-    for (long long b = slot; b < blocks; b += 16) neumaier_add(sum, comp, part[b * ppad + p]);
-  red[threadIdx.x] = sum + comp;
-  __syncthreads();
-  for (int o = 8; o > 0; o >>= 1) {
-    if (slot < o) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + 16 * o];
-    __syncthreads();
-  }
+    for (long long b = slot; b < blocks; b += 16) acc.add(0, part[b * ppad + p]);
+  red[threadIdx.x] = acc.total(0);
+  block_tree<256, 1, 16>(red);
   if (slot == 0 && p < P) out[p] = red[threadIdx.x];
 }
 
 // ---- permuted dot products ---------------------------------------------------------------------------------------------------------
 // Block p: out[p] = sum_i (k_i - shift) (l_pi_p(i) - shift), shift = 0 or 1 (the unbiased estimator's k~, l~); thread t adds the rows
-// t, t + 256, ... with a compensated sum, then a fixed tree
+// t, t + 256, ... with a compensated sum, then the block tree
 __global__ __launch_bounds__(256) void hsic_dots_kernel(const double* __restrict__ k, const double* __restrict__ l, int n,
                                                         const int* __restrict__ perm, double shift, double* __restrict__ out) {
   __shared__ double red[256];
   const int* row = perm ? perm + (long long)blockIdx.x * n : nullptr;
-  double sum = 0.0, comp = 0.0;
+  NeumaierSums<1> acc;
   for (int i = threadIdx.x; i < n; i += 256) {
     const double a = k[i] - shift;
     const double b = l[row ? row[i] : i] - shift;
-    neumaier_add(sum, comp, a * b);
+    acc.add(0, a * b);
   }
-  red[threadIdx.x] = sum + comp;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + o];
-    __syncthreads();
-  }
+  red[threadIdx.x] = acc.total(0);
+  block_tree<256, 1>(red);
   if (threadIdx.x == 0) out[blockIdx.x] = red[0];
 }
 

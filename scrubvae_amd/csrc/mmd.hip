@@ -9,12 +9,13 @@
 // recomputing the distances; the histogram is global, so a pass is one launch over all tiles plus a one-block scan that writes
 // the next prefix and rank to device memory.  Kernel value of a pair: exp((-(dist * dist)) / h).  kxx, kyy, kxy = the means over
 // the pairs inside X, inside Y and across; result kxx + kyy - 2 kxy.  Sums go to per-block partials at fixed positions and are
-// reduced in a fixed order; the histogram counts are integer atomics.  Nothing depends on scheduling.
+// reduced in the fixed orders of fixed_sum.h; the histogram counts are integer atomics.  Nothing depends on scheduling.
 #include "svae_internal.h"
 
 #include <algorithm>
 
 #include "pair_tiles.h"  // the tile walk and #pragma clang fp contract(off)
+#include "fixed_sum.h"   // the closing sums
 #include "mmd_common.h"  // mmd_value, mmd_statistic
 
 namespace svae {
@@ -199,35 +200,23 @@ __global__ __launch_bounds__(256) void mmd_sums_kernel(const double* __restrict_
   }
 #pragma unroll
   for (int k = 0; k < 3; ++k) red[k * 256 + threadIdx.x] = a[k];
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o)
-#pragma unroll
-      for (int k = 0; k < 3; ++k) red[k * 256 + threadIdx.x] = red[k * 256 + threadIdx.x] + red[k * 256 + threadIdx.x + o];
-    __syncthreads();
-  }
+  block_tree<256, 3>(red);
   if (threadIdx.x < 3) part[3 * block + threadIdx.x] = red[threadIdx.x * 256];
 }
 
-// One block: thread t adds the partials of blocks t, t + 1024, ... with a compensated (Neumaier) sum, then a fixed tree.
+// One block: thread t adds the partials of blocks t, t + 1024, ... compensated, then the block tree (fixed_sum.h).
 // out = {kxx, kyy, kxy, kxx + kyy - 2 kxy}
 __global__ __launch_bounds__(1024) void mmd_reduce_kernel(const double* __restrict__ part, long long blocks, int nx, int ny,
                                                           double* __restrict__ out) {
   __shared__ double red[3 * 1024];
-  double sum[3] = {0.0, 0.0, 0.0}, comp[3] = {0.0, 0.0, 0.0};
+  NeumaierSums<3> acc;
   for (long long b = threadIdx.x; b < blocks; b += 1024) {
 #pragma unroll
-    for (int k = 0; k < 3; ++k) neumaier_add(sum[k], comp[k], part[3 * b + k]);
+    for (int k = 0; k < 3; ++k) acc.add(k, part[3 * b + k]);
   }
 #pragma unroll
-  for (int k = 0; k < 3; ++k) red[k * 1024 + threadIdx.x] = sum[k] + comp[k];
-  __syncthreads();
-  for (int o = 512; o > 0; o >>= 1) {
-    if (threadIdx.x < o)
-#pragma unroll
-      for (int k = 0; k < 3; ++k) red[k * 1024 + threadIdx.x] = red[k * 1024 + threadIdx.x] + red[k * 1024 + threadIdx.x + o];
-    __syncthreads();
-  }
+  for (int k = 0; k < 3; ++k) red[k * 1024 + threadIdx.x] = acc.total(k);
+  block_tree<1024, 3>(red);
   if (threadIdx.x == 0) mmd_statistic(red[0], red[1024], red[2048], nx, ny, out);
 }
 

@@ -12,14 +12,16 @@
 // nx > n - nx), so the sum inside the small side is the direct one, and the two sums that take differences hold at least
 // n / 2 - 1 terms per row of R_i on average.  The statistic is symmetric in the sides, so the swap changes nothing else.
 // A product K_ij x {0, 1} is exact, so only the order of the additions matters, and the tile schedule fixes it: the MFMA's k
-// order within a tile, tiles in column order, the four rows of a lane, a fixed cross-lane tree, the four waves in order,
-// per-block partials at fixed positions, a compensated fixed-order reduction.  No floating-point atomics.  A column's value
-// depends on its own label bits only: not on its neighbours, its position in the chunk or the chunk it falls in.
+// order within a tile, tiles in column order, the four rows of a lane, a fixed cross-lane tree, then the orders of fixed_sum.h:
+// the four waves in order, per-block partials at fixed positions, compensated strided sums and the tree over their 16 slots.
+// No floating-point atomics.  A column's value depends on its own label bits only: not on its neighbours, its position in the
+// chunk or the chunk it falls in.
 #include "svae_internal.h"
 
 #include <algorithm>
 
 #include "pair_tiles.h"  // the tile walk, the A-operand tile and #pragma clang fp contract(off)
+#include "fixed_sum.h"   // the closing sums
 #include "mmd_common.h"  // mmd_value, mmd_statistic
 
 namespace svae {
@@ -135,33 +137,24 @@ __global__ __launch_bounds__(256) void mmd_null_kernel(const double* __restrict_
   }
   __syncthreads();
 #pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double* r = kt + k * 4 * NPC + threadIdx.x;
-    out[k * kind] = ((r[0] + r[NPC]) + r[2 * NPC]) + r[3 * NPC];
-  }
+  for (int k = 0; k < 3; ++k) out[k * kind] = waves4(kt + k * 4 * NPC + threadIdx.x, NPC);
 }
 
 // Block b: columns [16 b, 16 b + 16).  Thread (column c = t & 15, slot s = t >> 4) adds the partials of blocks s, s + 16, ... with a
-// compensated (Neumaier) sum, then a fixed tree over the 16 slots (na rows on the marked side, nb on the other).
+// compensated sum, then the block tree stopped at the 16 columns (fixed_sum.h); na rows on the marked side, nb on the other.
 __global__ __launch_bounds__(256) void mmd_null_reduce_kernel(const double* __restrict__ part, long long blocks, int ppad, int P,
                                                               int na, int nb, double* __restrict__ out) {
   __shared__ double red[3 * 256];
   const int slot = threadIdx.x >> 4;
   const int p = (int)blockIdx.x * 16 + (threadIdx.x & 15);  // < ppad: ppad is a multiple of NPC
-  double sum[3] = {0.0, 0.0, 0.0}, comp[3] = {0.0, 0.0, 0.0};
+  NeumaierSums<3> acc;
   for (long long b = slot; b < blocks; b += 16) {
 #pragma unroll
-    for (int k = 0; k < 3; ++k) neumaier_add(sum[k], comp[k], part[(k * blocks + b) * ppad + p]);
+    for (int k = 0; k < 3; ++k) acc.add(k, part[(k * blocks + b) * ppad + p]);
   }
 #pragma unroll
-  for (int k = 0; k < 3; ++k) red[k * 256 + threadIdx.x] = sum[k] + comp[k];
-  __syncthreads();
-  for (int o = 8; o > 0; o >>= 1) {
-    if (slot < o)
-#pragma unroll
-      for (int k = 0; k < 3; ++k) red[k * 256 + threadIdx.x] = red[k * 256 + threadIdx.x] + red[k * 256 + threadIdx.x + 16 * o];
-    __syncthreads();
-  }
+  for (int k = 0; k < 3; ++k) red[k * 256 + threadIdx.x] = acc.total(k);
+  block_tree<256, 3, 16>(red);
   if (slot == 0 && p < P) out[p] = mmd_statistic(red[threadIdx.x], red[256 + threadIdx.x], red[512 + threadIdx.x], na, nb, nullptr);
 }
 

@@ -15,6 +15,7 @@
 #include <algorithm>
 
 #include "pair_tiles.h"  // the tile walk, the A-operand tile and #pragma clang fp contract(off)
+#include "fixed_sum.h"   // the closing sum of the mean
 
 namespace svae {
 
@@ -119,18 +120,11 @@ __global__ __launch_bounds__(256) void sil_finish_kernel(const double* __restric
   nearest[r] = bc;
 }
 
-// out[0] = mean of v [n]: thread t adds v[t], v[t + 256], ... with a compensated (Neumaier) sum, then a fixed tree
+// out[0] = mean of v [n], summed by one block in the order of block_sum_of (fixed_sum.h)
 __global__ __launch_bounds__(256) void sil_mean_kernel(const double* __restrict__ v, long long n, double* __restrict__ out) {
   __shared__ double red[256];
-  double sum = 0.0, comp = 0.0;
-  for (long long i = threadIdx.x; i < n; i += 256) neumaier_add(sum, comp, v[i]);
-  red[threadIdx.x] = sum + comp;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[0] = red[0] / (double)n;
+  const double sum = block_sum_of<256>(v, n, red);
+  if (threadIdx.x == 0) out[0] = sum / (double)n;
 }
 
 // a >= +0 and finite: its bits order as unsigned integers.  key[c] = the smallest a of cluster c, then row[c] = the lowest row

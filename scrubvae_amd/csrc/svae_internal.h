@@ -84,13 +84,6 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   return v;
 }
 
-// One step of a compensated (Neumaier) sum; the total is sum + comp.  Additions only: nothing for the compiler to contract.
-__device__ __forceinline__ void neumaier_add(double& sum, double& comp, double v) {
-  const double tsum = sum + v;
-  comp = comp + (fabs(sum) >= fabs(v) ? (sum - tsum) + v : (v - tsum) + sum);
-  sum = tsum;
-}
-
 // block-wide sum for blockDim.x == 256 (4 waves); result valid in thread 0
 __device__ __forceinline__ float block_sum_256(float v, float* smem4) {
   v = wave_sum(v);

@@ -14,6 +14,8 @@
 #include <algorithm>
 #include <cmath>
 
+#include "fixed_sum.h"  // the closing sums
+
 #pragma clang fp contract(off)
 
 namespace svae {
@@ -118,20 +120,12 @@ __global__ __launch_bounds__(256) void tsne_repulsion_finish_kernel(const double
   rowq[i] = s[2];
 }
 
-// block b: out[b] = the sum of v_b [n]; thread t adds v[t], v[t + 256], ... with a compensated (Neumaier) sum, then a fixed tree
+// block b: out[b] = the sum of v_b [n] in the order of block_sum_of (fixed_sum.h)
 __global__ __launch_bounds__(256) void tsne_sums_kernel(const double* __restrict__ a, const double* __restrict__ b, long long n,
                                                         double* __restrict__ out) {
   __shared__ double red[256];
-  const double* v = blockIdx.x == 0 ? a : b;
-  double sum = 0.0, comp = 0.0;
-  for (long long i = threadIdx.x; i < n; i += 256) neumaier_add(sum, comp, v[i]);
-  red[threadIdx.x] = sum + comp;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[blockIdx.x] = red[0];
+  const double sum = block_sum_of<256>(blockIdx.x == 0 ? a : b, n, red);
+  if (threadIdx.x == 0) out[blockIdx.x] = sum;
 }
 
 // One row per thread: the row's entries in stored order.  Reads Y, writes update and gains (the row's own) only.
