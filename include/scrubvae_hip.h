@@ -787,6 +787,35 @@ int svae_hsic_cross(const double* Z, int ld, int d, int n, const double* hz, con
                     const double* hy, const int* perm, int P, double* work, double* out, void* stream);
 int svae_hsic_dots(const double* k, const double* l, int n, const int* perm, int P, int tilde, double* out, void* stream);
 
+/* ------------------------------------------------------- Mutual information of latents and a variable by kNN (csrc/mi.hip) ---- */
+/* The k-nearest-neighbour estimators of I(z; y) in their integer parts: Kraskov-Stoegbauer-Grassberger (algorithm 1) for a real y,
+ * Ross (2014) for labels.  Z [n][ld] fp64 rows, not centred, d >= 1, 2 <= n < 2^31, 1 <= k <= min(n - 1, SVAE_MI_MAX_K).  The
+ * variable is either Y [n][q] fp64 rows, contiguous, 1 <= q <= SVAE_MI_MAX_Y, or lab [n] int32.  s^z_ij and s^y_ij are the squared
+ * distances of csrc/pair_tiles.h (feature order, no FMA), compared by their uint64 bit patterns, never by a square root.  The row
+ * itself is left out by index, not by distance: a duplicate of row i counts at 0.
+ *
+ * svae_mi_radius: rho2 [n].  With Y: the k-th smallest max(s^z_ij, s^y_ij) over j != i.  With lab: the kk[i]-th smallest s^z_ij
+ * over the j != i with lab[j] == lab[i]; kk [n] int32, 1 <= kk[i] <= k, and the caller guarantees that row i has at least kk[i]
+ * such candidates (with fewer, rho2[i] is left unwritten).  Exactly one of Y and lab is non-null; kk is given with lab only.  One
+ * pass over the n^2 distances with the running best k of 64 rows in LDS, as svae_knn (csrc/knn_buffer.h: 64 rows x 128 buffered
+ * candidates, of which a tile of 64 columns may add 64 to a row; SVAE_MI_MAX_K = 32 leaves a cut buffer two tiles at least).
+ * svae_mi_counts: nz [n] = #{j != i : s^z_ij < rho2[i]} and, with Y, ny [n] = #{j != i : s^y_ij < rho2[i]}, both strict (a row
+ * with rho2 = 0 counts 0).  Y and ny are both null for labels.  A second all-pairs pass; int32 counts combined by integer adds
+ * only, so exact and independent of scheduling and of the column chunks.
+ * svae_mi_psi_sums: out[0] = sum_i psi(a[i] + 1), out[1] = sum_i psi(b[i] + 1) (b nullable), a and b [n] int32 >= 0: compensated
+ * sums at fixed positions, then a fixed tree, as svae_tsne_sums.  psi(m) of a positive integer: for m < 16,
+ * -0.5772156649015329 + (1/1 + ... + 1/(m - 1)) added in ascending order; from 16 on, with x = m and t = 1 / (x x),
+ * log(x) - 0.5 / x - t (1/12 - t (1/120 - t (1/252 - t (1/240 - t / 132)))), no FMA. */
+#define SVAE_MI_MAX_K 32
+#define SVAE_MI_MAX_Y 4
+/* bytes of work that svae_mi_radius needs (0 for n < 2, k < 1, k > n - 1 or k > SVAE_MI_MAX_K): column chunks (at most 8, 1 once
+ * the grid holds 512 blocks) x rows padded to 64 x k x 12 (a uint64 key and an int32 index per kept candidate) */
+long long svae_mi_work(int n, int k);
+int svae_mi_radius(const double* Z, int ld, int d, int n, const double* Y, int q, const int* lab, const int* kk, int k, void* work,
+                   double* rho2, void* stream);
+int svae_mi_counts(const double* Z, int ld, int d, int n, const double* Y, int q, const double* rho2, int* nz, int* ny, void* stream);
+int svae_mi_psi_sums(const int* a, const int* b, long long n, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

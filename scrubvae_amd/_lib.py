@@ -214,6 +214,10 @@ SIGNATURES = {
     "svae_hsic_moments": (I, [P, I, I, P, I, P, P, P, P, P]),
     "svae_hsic_cross": (I, [P, I, I, I, P, P, I, P, P, P, I, P, P, P]),
     "svae_hsic_dots": (I, [P, P, I, P, I, I, P, P]),
+    "svae_mi_work": (LL, [I, I]),
+    "svae_mi_radius": (I, [P, I, I, I, P, I, P, P, I, P, P, P]),
+    "svae_mi_counts": (I, [P, I, I, I, P, I, P, P, P, P]),
+    "svae_mi_psi_sums": (I, [P, P, LL, P, P]),
 }
 
 _lib = None
@@ -251,6 +255,7 @@ MMD_WORK_WORDS = 8256  # include/scrubvae_hip.h SVAE_MMD_WORK_WORDS
 MMD_NULL_MAX = 65536  # include/scrubvae_hip.h SVAE_MMD_NULL_MAX
 SIL_MAX_CLUSTERS = 4096  # include/scrubvae_hip.h SVAE_SIL_MAX_CLUSTERS
 KNN_MAX_K = 90  # include/scrubvae_hip.h SVAE_KNN_MAX_K
+MI_MAX_K, MI_MAX_Y = 32, 4  # include/scrubvae_hip.h SVAE_MI_*
 TSNE_SEARCH_STEPS, TSNE_MAX_CHUNKS = 100, 8  # include/scrubvae_hip.h SVAE_TSNE_*
 HSIC_MAX_Y, HSIC_PERMS = 4, 16  # include/scrubvae_hip.h SVAE_HSIC_*
 MAX_LOSS_TERMS = 48  # include/scrubvae_hip.h SVAE_MAX_LOSS_TERMS

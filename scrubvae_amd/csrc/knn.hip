@@ -4,78 +4,30 @@
 // key is strict, so the neighbour set is unique, and the lists are written in key order: nothing depends on thread scheduling or on
 // how the columns are split, and no floating-point sum is involved.
 //
-// A block owns 64 rows (lane = row) and walks its column tiles in ascending order.  Every row has a buffer of KNN_CAP candidates
-// in LDS, entry-major (entry e of row r at [e * 64 + r]: conflict-free for the lanes of a wave), filled through a per-row LDS
-// counter because the four waves see different candidates of the same row.  Each lane holds the s of its row's current k-th key as
-// a threshold and appends only candidates strictly below it: a later candidate with the same s has a higher index than the k-th
-// key, which came from an earlier tile, so it can never displace it.  When some row's buffer could overflow at the next tile (more
-// than KNN_CAP - 64 entries: a block-uniform test) every buffer with more than k entries is cut to its k smallest keys and the
-// thresholds tighten.  After t tiles a row accepts about k / t candidates per tile, so cuts become rare quickly and the distance
-// arithmetic bounds the kernel.  At the end each block writes its rows' lists, sorted, to the work buffer, and knn_finish_kernel
-// merges the lists of the column chunks of a row by rank (a plain copy when there is one chunk) and takes the square roots.
+// A block owns 64 rows (lane = row) and walks its column tiles in ascending order, with the running best k of every row in the LDS
+// buffer of knn_buffer.h (KNN_CAP candidates per row, appended below a per-lane threshold, cut to the k smallest when a buffer could
+// overflow at the next tile).  After t tiles a row accepts about k / t candidates per tile, so cuts become rare quickly and the
+// distance arithmetic bounds the kernel.  At the end each block writes its rows' lists, sorted, to the work buffer, and
+// knn_finish_kernel merges the lists of the column chunks of a row by rank (a plain copy when there is one chunk) and takes the
+// square roots.
 #include "svae_internal.h"
 
-#include <algorithm>
-
-#include "pair_tiles.h"  // the tile walk and #pragma clang fp contract(off)
+#include "knn_buffer.h"  // pair_tiles.h: the tile walk and #pragma clang fp contract(off)
 
 namespace svae {
 
 constexpr int KNN_NGY = 8;        // column chunks per row tile at most
 constexpr int KNN_BLOCKS = 512;   // grid y splits the column tiles only while the grid holds fewer blocks than this
 constexpr int KNN_CAP = 154;      // buffered candidates per row
-constexpr int KNN_FULL = KNN_CAP - HT;  // a buffer holding more than this could overflow at the next tile
-constexpr int KNN_PAD = INT_MAX;  // index of the padding behind a list of fewer than k candidates (n < 2^31: no row has it)
-static_assert(SVAE_KNN_MAX_K <= KNN_FULL, "a buffer cut to k entries takes one more tile");
+typedef KnnBuffer<KNN_CAP> KnnBuf;
+static_assert(SVAE_KNN_MAX_K <= KnnBuf::FULL, "a buffer cut to k entries takes one more tile");
 
 // dynamic LDS, in doubles, after the rows and candidates of pair_tiles.h (the kt region is not used)
-constexpr int N_KEY = PAIR_LDS_KT;                // bkey [KNN_CAP][64] uint64
-constexpr int N_IDX = N_KEY + KNN_CAP * HR;       // bidx [KNN_CAP][64] int32
-constexpr int N_CNT = N_IDX + KNN_CAP * HR / 2;   // cnt  [64] uint32: entries in each row's buffer
-constexpr int N_THS = N_CNT + HR / 2;             // ths  [64] uint64: s of the row's k-th key (all ones: none yet; 0: no row)
-constexpr int N_THJ = N_THS + HR;                 // thj  [64] int32: its index
-constexpr int N_GRP = N_THJ + HR / 2;             // cgrp [64] int32: group of the tile's columns
+constexpr int N_KEY = PAIR_LDS_KT;                // the buffers of knn_buffer.h
+constexpr int N_GRP = N_KEY + KnnBuf::WORDS;      // cgrp [64] int32: group of the tile's columns
 constexpr int N_END = N_GRP + HT / 2;
 constexpr size_t KNN_LDS = (size_t)N_END * sizeof(double);  // 161,024 B: one block per CU, as hdb_core_kernel
 static_assert(KNN_LDS <= 160 * 1024, "LDS per workgroup");
-
-__device__ __forceinline__ bool knn_less(u64 ka, int ja, u64 kb, int jb) { return ka < kb || (ka == kb && ja < jb); }
-
-// Cuts every buffer with more than k entries to its k smallest keys and sets ths / thj to the k-th.  Wave w ranks the entries
-// w, w + 4, ... of its rows against the whole buffer to find the k-th key; then wave 0 moves the keys up to it to the front, in
-// place (an entry never moves to a higher position).  Block-uniform call; ends with the buffers and ths visible to every thread.
-__device__ __forceinline__ void knn_cut(u64* bkey, int* bidx, unsigned* cnt, u64* ths, int* thj, int k, int lane, int wave) {
-  const int m = (int)cnt[lane];
-  if (m > k) {
-    for (int e = wave; e < m; e += 4) {
-      const u64 k0 = bkey[e * HR + lane];
-      const int j0 = bidx[e * HR + lane];
-      int rank = 0;
-      for (int o = 0; o < m; ++o) rank += knn_less(bkey[o * HR + lane], bidx[o * HR + lane], k0, j0) ? 1 : 0;
-      if (rank == k - 1) {
-        ths[lane] = k0;
-        thj[lane] = j0;
-      }
-    }
-  }
-  __syncthreads();
-  if (wave == 0 && m > k) {
-    const u64 ts = ths[lane];
-    const int tj = thj[lane];
-    int w = 0;
-    for (int e = 0; e < m; ++e) {
-      const u64 ke = bkey[e * HR + lane];
-      const int je = bidx[e * HR + lane];
-      if (!knn_less(ts, tj, ke, je)) {  // key <= the k-th key
-        bkey[w * HR + lane] = ke;
-        bidx[w * HR + lane] = je;
-        ++w;
-      }
-    }
-    cnt[lane] = (unsigned)k;
-  }
-  __syncthreads();
-}
 
 // part_key / part_idx [(y * rpad + row) * k + e]: the k smallest keys of row `row` among the columns of chunk y, ascending, padded
 // with (all ones, KNN_PAD) where the chunk holds fewer than k candidates of the row
@@ -83,11 +35,7 @@ __global__ __launch_bounds__(256) void knn_lists_kernel(const double* __restrict
                                                         const int* __restrict__ group, int ch, long long rpad,
                                                         u64* __restrict__ part_key, int* __restrict__ part_idx) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
-  u64* bkey = reinterpret_cast<u64*>(lds + N_KEY);
-  int* bidx = reinterpret_cast<int*>(lds + N_IDX);
-  unsigned* cnt = reinterpret_cast<unsigned*>(lds + N_CNT);
-  u64* ths = reinterpret_cast<u64*>(lds + N_THS);
-  int* thj = reinterpret_cast<int*>(lds + N_THJ);
+  const KnnBuf buf(lds + N_KEY);
   int* cgrp = reinterpret_cast<int*>(lds + N_GRP);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long r0 = (long long)blockIdx.x * HR;
@@ -96,12 +44,7 @@ __global__ __launch_bounds__(256) void knn_lists_kernel(const double* __restrict
   const int t_lo = (int)blockIdx.y * ch, t_hi = min(((int)blockIdx.y + 1) * ch, pair_tile_count(n));
   const int mygrp = group && ok ? group[r] : 0;
   const PairRows rows = pair_rows(Z, ld, d, n, r0, lds + PAIR_LDS_QS, lds + PAIR_LDS_CS);
-  if (threadIdx.x < HR) {
-    cnt[lane] = 0u;
-    ths[lane] = ok ? ~0ull : 0ull;  // a lane past n accepts nothing
-    thj[lane] = KNN_PAD;
-  }
-  u64 thr = ok ? ~0ull : 0ull;
+  u64 thr = buf.reset(ok, lane);
   for (int ct = t_lo; ct < t_hi; ++ct) {
     const long long c0 = (long long)ct * HT;
     // the previous tile's reads of cgrp ended at the barrier after its appends; the barriers of pair_tile publish this write
@@ -114,40 +57,18 @@ __global__ __launch_bounds__(256) void knn_lists_kernel(const double* __restrict
       if (key < thr) {
         const int cl = wave * HQ + q;
         const long long c = c0 + cl;
-        if (c < n && c != r && !(group && cgrp[cl] == mygrp)) {
-          const unsigned pos = atomicAdd(&cnt[lane], 1u);  // < KNN_CAP: at most KNN_FULL before the tile, at most 64 added
-          bkey[pos * HR + lane] = key;
-          bidx[pos * HR + lane] = (int)c;
-        }
+        if (c < n && c != r && !(group && cgrp[cl] == mygrp)) buf.append(lane, key, (int)c);
       }
     }
     __syncthreads();
-    if (__any((int)cnt[lane] > KNN_FULL)) {  // every wave reads the same 64 counters: block-uniform
-      knn_cut(bkey, bidx, cnt, ths, thj, k, lane, wave);
-      thr = ths[lane];
+    if (buf.could_overflow(lane)) {
+      buf.cut(k, lane, wave);
+      thr = buf.ths[lane];
     }
   }
   __syncthreads();  // an empty tile range comes here straight from the setup
-  knn_cut(bkey, bidx, cnt, ths, thj, k, lane, wave);
-  // at most k entries per row now: write them in key order, by rank
-  const int m = (int)cnt[lane];
-  if (ok) {
-    u64* out_key = part_key + ((long long)blockIdx.y * rpad + r) * k;
-    int* out_idx = part_idx + ((long long)blockIdx.y * rpad + r) * k;
-    for (int e = wave; e < k; e += 4) {
-      if (e < m) {
-        const u64 k0 = bkey[e * HR + lane];
-        const int j0 = bidx[e * HR + lane];
-        int rank = 0;
-        for (int o = 0; o < m; ++o) rank += knn_less(bkey[o * HR + lane], bidx[o * HR + lane], k0, j0) ? 1 : 0;
-        out_key[rank] = k0;
-        out_idx[rank] = j0;
-      } else {
-        out_key[e] = ~0ull;
-        out_idx[e] = KNN_PAD;
-      }
-    }
-  }
+  buf.cut(k, lane, wave);
+  if (ok) buf.write_sorted(k, lane, wave, part_key + ((long long)blockIdx.y * rpad + r) * k, part_idx + ((long long)blockIdx.y * rpad + r) * k);
 }
 
 // One thread per (row, position e): the entry at e of each chunk's list goes to its rank among all the chunks' entries of the row,
@@ -168,13 +89,7 @@ __global__ __launch_bounds__(256) void knn_finish_kernel(const u64* __restrict__
     for (int y2 = 0; y2 < gy && rank < k; ++y2) {
       if (y2 == y) continue;
       const long long b2 = ((long long)y2 * rpad + row) * k;
-      int lo = 0, hi = k;
-      while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (knn_less(part_key[b2 + mid], part_idx[b2 + mid], k0, j0)) lo = mid + 1;
-        else hi = mid;
-      }
-      rank += lo;
+      rank += knn_count_below(part_key, part_idx, b2, k, k0, j0);
     }
     if (rank < k) {
       idx[row * k + rank] = j0;
@@ -187,22 +102,7 @@ __global__ __launch_bounds__(256) void knn_finish_kernel(const u64* __restrict__
 
 using namespace svae;
 
-struct KnnPlan {
-  int ch;
-  unsigned gx, gy;
-  long long rpad;
-};
-
-static KnnPlan knn_plan(int n) {
-  KnnPlan p;
-  const int nt = pair_tile_count(n);
-  p.gx = (unsigned)nt;
-  const int want = (int)std::min<long long>(std::min(nt, KNN_NGY), (KNN_BLOCKS + (long long)nt - 1) / nt);
-  p.ch = (nt + want - 1) / want;
-  p.gy = (unsigned)((nt + p.ch - 1) / p.ch);
-  p.rpad = (long long)nt * HR;
-  return p;
-}
+static KnnPlan knn_plan(int n) { return knn_plan(n, KNN_NGY, KNN_BLOCKS); }
 
 static bool knn_sizes_ok(int n, int k) { return n >= 2 && k >= 1 && k <= SVAE_KNN_MAX_K && k <= n - 1; }
 

@@ -6,5 +6,6 @@ from .independence import HSICPermutationResult, hsic, hsic_bandwidth, hsic_perm
 from .metrics import (cluster_entropy, hungarian_match, knn_class_rand_cv, knn_reg_rand_cv, lda_rand_cv, linear_rand_cv,  # noqa: F401
                       log_class_rand_cv, mlp_rand_cv, mmd_bandwidth, mmd_estimate, mmd_permutation_test, mmd_permutations,
                       qda_rand_cv, shannon_entropy)
+from .mutual_info import MIPermutationResult, latent_mi_scores, mutual_information, mutual_information_permutation_test  # noqa: F401
 from .neighbors import kneighbors, kneighbors_graph, knn_label_purity  # noqa: F401
 from .silhouette import cluster_medoids, cluster_silhouette, silhouette_samples, silhouette_score  # noqa: F401
