@@ -816,6 +816,28 @@ int svae_mi_radius(const double* Z, int ld, int d, int n, const double* Y, int q
 int svae_mi_counts(const double* Z, int ld, int d, int n, const double* Y, int q, const double* rho2, int* nz, int* ny, void* stream);
 int svae_mi_psi_sums(const int* a, const int* b, long long n, double* out, void* stream);
 
+/* ------------------------------------------------------- Ranks of given neighbours; embedding-quality sums (csrc/rank.hip) ---- */
+/* svae_knn_ranks: X [n][ld] fp64 rows, not centred, d >= 1, 2 <= n < 2^31; idx [n][k] int32, 1 <= k <= min(n - 1, SVAE_KNN_MAX_K),
+ * row i holding k distinct indices in [0, n), none equal to i.  rank [n][k] int32:
+ *   rank[i][m] = 1 + #{l != i : key(i, l) < key(i, idx[i][m])}
+ * with the strict key of svae_knn: the squared distance of csrc/pair_tiles.h (feature order, no FMA) compared by its uint64 bit
+ * pattern, then the lower index.  Rank 1 is the nearest other row, rank n - 1 the farthest; the ranks of a row are distinct, and
+ * with idx = the row's own svae_knn list they are 1..k.  One all-pairs pass with the sorted thresholds and a histogram of 64 rows
+ * in LDS (41,472 B of staged rows + 128 k x 8 B: 133,632 B at k = 90), integer adds only: the result is exact and does not depend
+ * on scheduling, on the column chunks or on the order of a row's entries.  Nothing of size n^2 is stored.  The caller guarantees
+ * the conditions on idx; an entry that is out of range or equal to its row reads nothing and gets rank n, and a repeated entry
+ * gets its one rank in both columns.
+ * svae_rank_curves: from rank [n][k] (n >= 1, 1 <= k <= SVAE_KNN_MAX_K) whose column m belongs to the neighbour of order m + 1 in
+ * the other space, for kk = 1..k:  pen[kk - 1] = sum_i sum_{m < kk} max(0, rank[i][m] - kk)  and
+ * hit[kk - 1] = sum_i #{m < kk : rank[i][m] <= kk}, int64, by integer adds only.  With 1 <= row_k <= k, pen_row [n] int64
+ * receives the inner sum of pen for kk = row_k per row; row_k = 0 and pen_row = NULL ask for none. */
+/* bytes of work that svae_knn_ranks needs (0 for n < 2, k < 1, k > n - 1 or k > SVAE_KNN_MAX_K): n x k x 16 for the sorted
+ * thresholds (a uint64 key, an int32 index and an int32 column each) + column chunks (at most 8, 1 once the grid holds 512
+ * blocks) x n x k x 4 for the histograms */
+long long svae_rank_work(int n, int k);
+int svae_knn_ranks(const double* X, int ld, int d, int n, const int* idx, int k, void* work, int* rank, void* stream);
+int svae_rank_curves(const int* rank, int n, int k, int row_k, long long* pen, long long* hit, long long* pen_row, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

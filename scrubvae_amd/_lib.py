@@ -218,6 +218,9 @@ SIGNATURES = {
     "svae_mi_radius": (I, [P, I, I, I, P, I, P, P, I, P, P, P]),
     "svae_mi_counts": (I, [P, I, I, I, P, I, P, P, P, P]),
     "svae_mi_psi_sums": (I, [P, P, LL, P, P]),
+    "svae_rank_work": (LL, [I, I]),
+    "svae_knn_ranks": (I, [P, I, I, I, P, I, P, P, P]),
+    "svae_rank_curves": (I, [P, I, I, I, P, P, P, P]),
 }
 
 _lib = None

@@ -1,5 +1,6 @@
 from .cluster import GaussianMixture, dbscan, gmm  # noqa: F401
 from .embed import TSNE, tsne, tsne_affinities  # noqa: F401
+from .embed_quality import EmbeddingQuality, continuity, embedding_quality, neighbor_ranks, trustworthiness  # noqa: F401
 from .eval import generative_restrictiveness  # noqa: F401
 from .hdbscan import HDBSCAN  # noqa: F401
 from .independence import HSICPermutationResult, hsic, hsic_bandwidth, hsic_permutation_test  # noqa: F401
