@@ -838,6 +838,23 @@ long long svae_rank_work(int n, int k);
 int svae_knn_ranks(const double* X, int ld, int d, int n, const int* idx, int k, void* work, int* rank, void* stream);
 int svae_rank_curves(const int* rank, int n, int k, int row_k, long long* pen, long long* hit, long long* pen_row, void* stream);
 
+/* ------------------------------------------------------- Kernel density of a 2-D embedding on a grid (csrc/density.hip) ----- */
+/* Y [n][ld] fp64 points of the plane (ld >= 2, columns 0 and 1 are read), n >= 1; bandwidths h_rows [n], all > 0, or, with
+ * h_rows = NULL, the one h > 0 (h^2 and 1 / (2 h^2) finite and positive).  The grid is x_a = x0 + a dx for a < gx and
+ * y_b = y0 + b dy for b < gy, each node formed so in fp64 (one product, one sum), dx, dy > 0, 2 <= gx, gy <= SVAE_DENSITY_MAX_GRID.
+ * D [gy][gx] fp64, row-major:
+ *   D[b][a] = (1 / n) sum_i (1 / (2 pi h_i^2)) exp(-(x_a - Y[i][0])^2 / (2 h_i^2)) exp(-(y_b - Y[i][1])^2 / (2 h_i^2))
+ * as the product B^T A of the two separable factors, generated 16 points at a time into LDS and multiplied on the fp64 matrix
+ * cores, one 128 x 128 tile of D and one slice of the points per block; the slices (a function of n, gx, gy alone, at most 128)
+ * are added in order.  Exact: no binning, no cutoff; a term that underflows is zero.  Bit-reproducible on every device. */
+#define SVAE_DENSITY_MAX_GRID 1024
+/* bytes of work that svae_density_grid needs (0 for n < 1 or a grid side outside 2..SVAE_DENSITY_MAX_GRID): slices x gy x gx x 8
+ * for the partial grids + n x 16 for the per-point factors */
+long long svae_density_work(int n, int gx, int gy);
+/* work: 16-byte aligned, D: 8-byte aligned (SVAE_ERR_ALIGN otherwise) */
+int svae_density_grid(const double* Y, int ld, int n, const double* h_rows /* NULL: use h */, double h, double x0, double dx, int gx,
+                      double y0, double dy, int gy, void* work, double* D, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -221,6 +221,8 @@ SIGNATURES = {
     "svae_rank_work": (LL, [I, I]),
     "svae_knn_ranks": (I, [P, I, I, I, P, I, P, P, P]),
     "svae_rank_curves": (I, [P, I, I, I, P, P, P, P]),
+    "svae_density_work": (LL, [I, I, I]),
+    "svae_density_grid": (I, [P, I, I, P, D, D, D, I, D, D, I, P, P, P]),
 }
 
 _lib = None
@@ -260,6 +262,7 @@ SIL_MAX_CLUSTERS = 4096  # include/scrubvae_hip.h SVAE_SIL_MAX_CLUSTERS
 KNN_MAX_K = 90  # include/scrubvae_hip.h SVAE_KNN_MAX_K
 MI_MAX_K, MI_MAX_Y = 32, 4  # include/scrubvae_hip.h SVAE_MI_*
 TSNE_SEARCH_STEPS, TSNE_MAX_CHUNKS = 100, 8  # include/scrubvae_hip.h SVAE_TSNE_*
+DENSITY_MAX_GRID = 1024  # include/scrubvae_hip.h SVAE_DENSITY_MAX_GRID
 HSIC_MAX_Y, HSIC_PERMS = 4, 16  # include/scrubvae_hip.h SVAE_HSIC_*
 MAX_LOSS_TERMS = 48  # include/scrubvae_hip.h SVAE_MAX_LOSS_TERMS
 ERR_SHAPE, ERR_ALIGN, ERR_WORKSPACE, ERR_LAUNCH, ERR_ARG = -1, -2, -3, -4, -5  # include/scrubvae_hip.h svae_status

@@ -1,4 +1,5 @@
 from .cluster import GaussianMixture, dbscan, gmm  # noqa: F401
+from .density import DensityGrid, DensityMap, density_map, density_regions  # noqa: F401
 from .embed import TSNE, tsne, tsne_affinities  # noqa: F401
 from .embed_quality import EmbeddingQuality, continuity, embedding_quality, neighbor_ranks, trustworthiness  # noqa: F401
 from .eval import generative_restrictiveness  # noqa: F401
