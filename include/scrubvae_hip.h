@@ -162,6 +162,10 @@ int svae_conv_wgrad_split(const svae_conv_desc* d, const float* x, const float* 
                           float* db, void* ws, size_t ws_bytes, int accumulate, int pieces, void* stream);
 /* introspection: tile, kernel variant and (halo variant) image rows of the split fwd (0) / dgrad (1) launch */
 int svae_conv_split_tile(const svae_conv_desc* d, int kind, int* bm, int* bn, int* variant, int* rmax);
+/* how the split fwd / dgrad kernels move their output tiles: 1 (default) = 16-byte loads and stores behind an LDS transposition
+ * in the kernels built with it, 0 = one dword per accumulator register.  Same values either way (A/B runs, tests).
+ * Process-wide; returns the previous setting */
+int svae_conv_epilogue_wide(int on);
 
 /* introspection: the (BM, BN) workgroup tile the dispatcher uses; kind 0 fwd, 1 dgrad, 2 wgrad */
 int svae_conv_tile(const svae_conv_desc* d, int kind, int* bm, int* bn);

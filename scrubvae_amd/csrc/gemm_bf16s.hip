@@ -27,6 +27,16 @@
 
 namespace svae {
 
+// Diagnostic build only (python scrubvae_amd/build.py --ablation; tools/stamp_epilogue.py): s_memtime stamps that bracket the
+// epilogue of gather_halo_bf16s_kernel in the workgroup (gridDim.x / 2, 0) -- per wave: kernel entry | stage loop done | epilogue's
+// last instruction issued | its stores drained -- written to a buffer of their own that nothing else reads.
+#ifdef SVAE_ABLATION_KERNELS
+__device__ unsigned long long* g_epi_stamp_buf = nullptr;
+#define SVAE_EPI_STAMP(i) do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(epi_t[i]) :: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
+#else
+#define SVAE_EPI_STAMP(i) do { } while (0)
+#endif
+
 
 // ------------------------------------------------------------------ gather GEMM (fwd / dgrad)
 // BM x BN tile per workgroup of WR x WC waves.  NSTAGE = 2: double-buffered LDS, one barrier per
@@ -227,7 +237,9 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void gather_gemm_bf16s_kernel(c
     }
   }
 
-  tile_epilogue<MT, NT, WM, WN, WR, BN>(g, acc, rowoff, n0, wr, wc, lr, h, reinterpret_cast<float*>(smem), tid, NTH, H ? F16_OSCALE : 1.f);
+  // the loop's last barrier is behind every wave's last operand read: the staging LDS is free for the epilogue's block turns
+  constexpr int XW = sizeof(smem) >= (NTH / 64) * 4096 ? NTH / 64 : 0;
+  tile_epilogue<MT, NT, WM, WN, WR, BN, XW>(g, acc, rowoff, n0, wr, wc, lr, h, reinterpret_cast<float*>(smem), tid, NTH, H ? F16_OSCALE : 1.f);
 }
 
 // ------------------------------------------------- gather GEMM, wave-specialised (fwd / dgrad)
@@ -507,6 +519,8 @@ __global__ __launch_bounds__(64 * WR * WC) void gather_halo_bf16s_kernel(const S
   __shared__ long long rowoff[BM];
 
   const int tid = threadIdx.x;
+  [[maybe_unused]] unsigned long long epi_t[4] = {0, 0, 0, 0};
+  SVAE_EPI_STAMP(0);
   int bx = blockIdx.x, phase = 0;
   if (bx >= g.blocks_m[0]) { phase = 1; bx -= g.blocks_m[0]; }
   const long long m0 = (long long)bx * BM;
@@ -798,8 +812,18 @@ __global__ __launch_bounds__(64 * WR * WC) void gather_halo_bf16s_kernel(const S
     if (++tap == ntaps) { tap = 0; ++kb; }
   }
   if (ns == 0) __syncthreads();  // rowoff
+  SVAE_EPI_STAMP(1);
 
-  tile_epilogue<MT, NT, WM, WN, WR, BN>(g, acc, rowoff, n0, wr, wc, lr, h, reinterpret_cast<float*>(smem), tid, NTH, H ? F16_OSCALE : 1.f);
+  // the loop's last barrier is behind every wave's last operand read: the staging LDS is free for the epilogue's block turns
+  constexpr int XW = sizeof(smem) >= (NTH / 64) * 4096 ? NTH / 64 : 0;
+  tile_epilogue<MT, NT, WM, WN, WR, BN, XW>(g, acc, rowoff, n0, wr, wc, lr, h, reinterpret_cast<float*>(smem), tid, NTH, H ? F16_OSCALE : 1.f);
+#ifdef SVAE_ABLATION_KERNELS
+  SVAE_EPI_STAMP(2);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  SVAE_EPI_STAMP(3);
+  if (g_epi_stamp_buf && blockIdx.x == gridDim.x / 2 && blockIdx.y == 0 && lane == 0)
+    for (int i = 0; i < 4; ++i) g_epi_stamp_buf[wave * 4 + i] = epi_t[i];
+#endif
 }
 
 // ---------------------------------------------------------------------------- weight split
@@ -891,6 +915,7 @@ __global__ __launch_bounds__(256) void split_weights_batched_kernel(const SplitT
 }
 
 // ------------------------------------------------------------------------------ host side
+static int g_epilogue_wide = 1;  // svae_conv_epilogue_wide: the epilogue's 16-byte path (GatherArgs.wide_epi)
 // layout of the split-weight buffer: [Wf: 3 bf16 planes][Wd: 3 bf16 planes][Wfh: 2 fp16 planes of 2^10 w], plane sizes in elements
 static inline long long plane_f(const svae_conv_desc* d) { return (long long)d->kernel * ((d->c_in + 31) / 32) * 32 * d->c_out; }
 static inline long long plane_d(const svae_conv_desc* d) { return (long long)d->kernel * ((d->c_out + 31) / 32) * 32 * d->c_in; }
@@ -949,6 +974,7 @@ static int launch_split_gather(SplitGatherArgs& sa, hipStream_t st, int code, in
   GatherArgs& g = sa.g;
   const SplitGeo geo = split_gather_geometry(g, code, pieces);
   for (int p = 0; p < 2; ++p) g.blocks_m[p] = geo.blocks_m[p];
+  g.wide_epi = g_epilogue_wide;
 #ifdef SVAE_ABLATION_KERNELS  // timing experiments with parts of the work removed (wrong results): python scrubvae_amd/build.py --ablation
   if (int e = 0; launch_split_halo_diag(sa, geo, st, pieces, &e)) return e;
 #endif
@@ -989,6 +1015,19 @@ static int launch_split_gather(SplitGatherArgs& sa, hipStream_t st, int code, in
 
 using namespace svae;
 
+
+#ifdef SVAE_ABLATION_KERNELS
+extern "C" int svae_debug_epilogue_stamp_buffer(void* buf) {  // diagnostic build only: [8 waves][4] ticks
+  unsigned long long* p = (unsigned long long*)buf;
+  return hipMemcpyToSymbol(HIP_SYMBOL(svae::g_epi_stamp_buf), &p, sizeof(p)) == hipSuccess ? SVAE_OK : SVAE_ERR_LAUNCH;
+}
+#endif
+
+extern "C" int svae_conv_epilogue_wide(int on) {
+  const int was = g_epilogue_wide;
+  g_epilogue_wide = on != 0;
+  return was;
+}
 
 extern "C" size_t svae_conv_split_bytes(const svae_conv_desc* d) {
   if (validate(d)) return 0;

@@ -44,6 +44,9 @@ struct GatherArgs {
   const float* bn_rstd;
   const float* bn_alpha;
   float* bn_dalpha;
+  // split-bf16 gather kernels: 1 = the epilogue moves C (and the old C / bn_x it reads) in 16-byte pieces through an LDS
+  // transposition where alignment allows (tile_epilogue, split_gather.h); 0 = one dword per accumulator register.  Same values.
+  int wide_epi;
 };
 
 inline int validate(const svae_conv_desc* d) {

@@ -18,12 +18,50 @@ struct SplitGatherArgs {
   float* up_out;              // g.up: where the upsampled operand rows go as a by-product ([rowsA][ldA], NULL: nowhere)
 };
 
+// One element's share of the epilogue's sums, with every rounding pinned: u = fma(x, scale, shift), 1 - t^2 = fma(-t, t, 1) and
+// the fp64 slope term are fused, while sum v^2 and sum du * xhat are a ROUNDED product added to the sum.  That is what every
+// instance of these kernels computed while the choice was the compiler's (it pairs (sum, sum of squares) into a packed add, which
+// keeps the multiply apart); pinned, because the two paths of one instance would otherwise be free to round differently.
+__device__ __forceinline__ void epilogue_sums(float v, float x, bool bwd, bool th, float slope, float sc, float sh, float mu, float rs,
+                                              float& cs, float& cq, double& da) {
+#pragma clang fp contract(off)
+  if (bwd) {
+    const float u = __builtin_fmaf(x, sc, sh);
+    float du;
+    if (th) { const float t = tanhf(u); du = v * __builtin_fmaf(-t, t, 1.f); }
+    else { du = u > 0.f ? v : slope * v; if (!(u > 0.f)) da = __builtin_fma((double)v, (double)u, da); }
+    cs += du;
+    const float p = du * (x - mu) * rs;
+    cq += p;
+  } else {
+    cs += v;
+    const float p = v * v;
+    cq += p;
+  }
+}
+
+__device__ __forceinline__ void wave_lds_turn() {  // orders this wave's LDS writes and reads of other lanes' elements (LDS serves a wave in order)
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
 // ---- epilogue shared by the gather kernels: C (+)= acc + bias, and -- when g.stats != NULL -- the BatchNorm batch statistics of
 // the values just written (reference: nn.BatchNorm1d in train mode right behind the conv, residual.py:88,112,146,173): per-column
 // (sum v, sum v^2) over the tile's valid rows go to stats[blockIdx.x][2][N], the layout bn_stats_partial writes per 128-row chunk,
 // so the finalize kernel sums row tiles instead of chunks and the separate statistics pass over the conv output disappears.
 // Fixed summation order (lane rows, the two half-waves, then the WR row-waves): bit-reproducible.
-template <int MT, int NT, int WM, int WN, int WR, int BN>
+//
+// XW > 0 (the kernel's staging LDS holds 4 KiB for each of its XW epilogue waves, and every wave is past its last operand read
+// when the epilogue starts): the wide path.  The 32 x 32 accumulator layout gives a lane ONE column and 16 rows of a block, so the
+// plain path moves one dword per register: 16 stores (and 16 loads each of the old C under accumulate and of bn_x) per block.  The
+// wide path turns each block through the wave's own 32 x 32 fp32 LDS region -- row stride 32 dwords: the 32 lanes of a
+// ds_write_b32 / ds_read_b32 group walk one row, and the 16 lanes of a ds_read_b128 group cover four 64-byte row halves on four
+// different bank quarters, so neither direction conflicts -- and moves it as 4 x 16 bytes per lane: lane = 4 consecutive columns
+// of row lane / 8 + 8 i.  The operands that come in take the reverse trip, all requested before the first one is turned.  Every value and every sum
+// is formed per element in the accumulator layout in the (nt, mt, r) order of the plain path: same bits.  Taken when
+// g.wide_epi is set, the epilogue READS (accumulate or fused sums: a launch that only stores gains nothing) and C, bn_x
+// and ldC are 16-byte aligned (wave-uniform); else the plain path.
+template <int MT, int NT, int WM, int WN, int WR, int BN, int XW = 0>
 __device__ __forceinline__ void tile_epilogue(const GatherArgs& g, f32x16 (&acc)[MT][NT], const long long* rowoff, int n0, int wr, int wc,
                                               int lr, int h, float* red, int tid, int nth, float oscale = 1.f, int tile_x = -1,
                                               int tile_y = 0) {
@@ -33,40 +71,100 @@ __device__ __forceinline__ void tile_epilogue(const GatherArgs& g, f32x16 (&acc)
   const bool bwd = g.bn_x != nullptr;        // uniform
   const bool th = g.bn_alpha == nullptr;     // tanh instead of PReLU
   const float slope = (bwd && !th) ? g.bn_alpha[0] : 0.f;
+  bool wide = false;
+  if constexpr (XW > 0)  // a launch that only stores gains nothing from the wide path
+    wide = g.wide_epi && (g.accumulate || bwd) && ((g.ldC | g.N) & 3) == 0 &&
+           ((reinterpret_cast<unsigned long long>(g.C) | reinterpret_cast<unsigned long long>(g.bn_x)) & 15) == 0;
+  if (wide) {
+    float* xs = red + (tid >> 6) * 1024;  // this wave's block [32 rows][32 columns]
+    const int qr = (tid & 63) >> 3, qc = (tid & 7) * 4;  // row layout: rows qr + 8 i, columns qc .. qc + 3
+    const bool acc_in = g.accumulate != 0;
 #pragma unroll
-  for (int nt = 0; nt < NT; ++nt) {
-    const int col = n0 + wc * WN + nt * 32 + lr;
-    cs[nt] = 0.f;
-    cq[nt] = 0.f;
-    if (col >= g.N) continue;
-    const float bv = g.bias ? g.bias[col] : 0.f;
-    float sc = 1.f, sh = 0.f, mu = 0.f, rs = 0.f;
-    if (bwd) {
-      if (g.bn_scale) { sc = g.bn_scale[col]; sh = g.bn_shift[col]; }
-      if (g.bn_mean) { mu = g.bn_mean[col]; rs = g.bn_rstd[col]; }
+    for (int nt = 0; nt < NT; ++nt) {
+      const int col = n0 + wc * WN + nt * 32 + lr;
+      const int c4 = n0 + wc * WN + nt * 32 + qc;
+      const bool col_ok = col < g.N;
+      cs[nt] = 0.f;
+      cq[nt] = 0.f;
+      if (n0 + wc * WN + nt * 32 >= g.N) continue;  // uniform: the block lies behind the matrix
+      const float bv = (col_ok && g.bias) ? g.bias[col] : 0.f;
+      float sc = 1.f, sh = 0.f, mu = 0.f, rs = 0.f;
+      if (bwd && col_ok) {
+        if (g.bn_scale) { sc = g.bn_scale[col]; sh = g.bn_shift[col]; }
+        if (g.bn_mean) { mu = g.bn_mean[col]; rs = g.bn_rstd[col]; }
+      }
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt) {
+        // what comes in: both requests first, then bn_x turns into registers and the old C stays in the region, where every
+        // lane replaces its own 16 elements by the new values
+        long long qoff[4];
+        float4 po[4], px[4];
+        float xv[16];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const long long off = rowoff[wr * WM + mt * 32 + qr + 8 * i];
+          qoff[i] = (off >= 0 && c4 < g.N) ? off + c4 : -1;
+          po[i] = px[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+          if (bwd && qoff[i] >= 0) px[i] = *reinterpret_cast<const float4*>(g.bn_x + qoff[i]);
+          if (acc_in && qoff[i] >= 0) po[i] = *reinterpret_cast<const float4*>(g.C + qoff[i]);
+        }
+        if (bwd) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) *reinterpret_cast<float4*>(xs + (qr + 8 * i) * 32 + qc) = px[i];
+          wave_lds_turn();
+#pragma unroll
+          for (int r = 0; r < 16; ++r) xv[r] = xs[((r & 3) + 8 * (r >> 2) + 4 * h) * 32 + lr];
+          wave_lds_turn();
+        }
+        if (acc_in) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) *reinterpret_cast<float4*>(xs + (qr + 8 * i) * 32 + qc) = po[i];
+          wave_lds_turn();
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int lrow = (r & 3) + 8 * (r >> 2) + 4 * h;
+          const long long off = rowoff[wr * WM + mt * 32 + lrow];
+          float v = __builtin_fmaf(acc[mt][nt][r], oscale, bv);
+          if (acc_in) v += xs[lrow * 32 + lr];
+          xs[lrow * 32 + lr] = v;
+          if (col_ok && off >= 0) epilogue_sums(v, bwd ? xv[r] : 0.f, bwd, th, slope, sc, sh, mu, rs, cs[nt], cq[nt], da);
+        }
+        wave_lds_turn();
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const float4 v4 = *reinterpret_cast<const float4*>(xs + (qr + 8 * i) * 32 + qc);
+          if (qoff[i] >= 0) *reinterpret_cast<float4*>(g.C + qoff[i]) = v4;
+        }
+        wave_lds_turn();
+      }
     }
+  }
+  if (!wide) {
 #pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
+    for (int nt = 0; nt < NT; ++nt) {
+      const int col = n0 + wc * WN + nt * 32 + lr;
+      cs[nt] = 0.f;
+      cq[nt] = 0.f;
+      if (col >= g.N) continue;
+      const float bv = g.bias ? g.bias[col] : 0.f;
+      float sc = 1.f, sh = 0.f, mu = 0.f, rs = 0.f;
+      if (bwd) {
+        if (g.bn_scale) { sc = g.bn_scale[col]; sh = g.bn_shift[col]; }
+        if (g.bn_mean) { mu = g.bn_mean[col]; rs = g.bn_rstd[col]; }
+      }
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = wr * WM + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-        const long long off = rowoff[row];
-        if (off >= 0) {
-          float* dst = g.C + off + col;
-          float v = acc[mt][nt][r] * oscale + bv;
-          if (g.accumulate) v += *dst;
-          *dst = v;
-          if (bwd) {
-            const float x = g.bn_x[off + col];
-            const float u = x * sc + sh;
-            float du;
-            if (th) { const float t = tanhf(u); du = v * (1.f - t * t); }
-            else { du = u > 0.f ? v : slope * v; if (!(u > 0.f)) da += (double)v * (double)u; }
-            cs[nt] += du;
-            cq[nt] += du * (x - mu) * rs;
-          } else {
-            cs[nt] += v;
-            cq[nt] += v * v;
+      for (int mt = 0; mt < MT; ++mt) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int row = wr * WM + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+          const long long off = rowoff[row];
+          if (off >= 0) {
+            float* dst = g.C + off + col;
+            float v = __builtin_fmaf(acc[mt][nt][r], oscale, bv);
+            if (g.accumulate) v += *dst;
+            *dst = v;
+            epilogue_sums(v, bwd ? g.bn_x[off + col] : 0.f, bwd, th, slope, sc, sh, mu, rs, cs[nt], cq[nt], da);
           }
         }
       }

@@ -174,6 +174,20 @@ _SPLIT_WGRAD_CODES = _SPLIT_WGRAD_CODES + (12128128, 12064128, 12128064, 1412812
 # BatchNorm batch statistics (forward) and first-pass backward sums from the conv GEMMs' epilogues where their kernels support it
 # (SVAE_FUSE_BN=0: the separate passes, for A/B measurements)
 FUSE_BN_STATS = os.environ.get("SVAE_FUSE_BN", "1") != "0"
+# SVAE_EPILOGUE_WIDE=0: the split forward / data-gradient kernels move their output tiles one dword per accumulator register
+# instead of in 16-byte pieces behind an LDS transposition (same values; for A/B measurements and tests)
+EPILOGUE_WIDE = os.environ.get("SVAE_EPILOGUE_WIDE", "1") != "0"  # env: experiments
+
+
+def set_epilogue_wide(on):
+    """Switch the 16-byte epilogue path of the split conv kernels (process-wide); returns the previous setting."""
+    global EPILOGUE_WIDE
+    EPILOGUE_WIDE = bool(on)
+    return bool(_lib.lib().svae_conv_epilogue_wide(int(EPILOGUE_WIDE)))
+
+
+if not EPILOGUE_WIDE:
+    set_epilogue_wide(False)
 MIX_F32 = True  # a bf16x6 conv may keep the fp32 MFMA kernel for a pass where that is faster (same accuracy)
 WEIGHT_EPOCH = 0  # bumped whenever master weights may have changed (start of every model pass)
 
