@@ -724,6 +724,18 @@ int svae_silhouette_medoids(const double* a, const int* lab, int n, int K, unsig
  * the grid holds 512 blocks) x rows padded to 64 x k x 12 (a uint64 key and an int32 index per kept candidate) */
 long long svae_knn_work(int n, int k);
 int svae_knn(const double* Z, int ld, int d, int n, int k, const int* group, void* work, int* idx, double* dist, void* stream);
+/* svae_knn_cross: the k nearest rows of X [n][ldx] for every row of Q [m][ldq], both of d >= 1 features, 1 <= m, n < 2^31,
+ * 1 <= k <= min(n, SVAE_KNN_MAX_K).  The neighbours of query i are the k smallest keys (s_ij, j) over ALL j < n, with svae_knn's
+ * strict key (the squared distance of csrc/pair_tiles.h by its bit pattern, then the lower j).  No row is left out: a query equal
+ * to a reference row has that row as a neighbour at distance 0 (Q = X gives every row itself first).  idx [m][k] and dist [m][k]
+ * are in ascending key order, dist the correctly rounded sqrt(s).  The same kernel walk and LDS buffer as svae_knn, without the
+ * self and group tests; the column chunks follow the same rule with the row tiles counted from m and the column tiles from n, and
+ * the key is strict, so the result does not depend on the split.
+ * svae_knn_cross_work: bytes of work (0 for m < 1, n < 1, k < 1, k > n or k > SVAE_KNN_MAX_K): column chunks (at most 8, 1 once
+ * the grid holds 512 blocks) x m padded to 64 x k x 12. */
+long long svae_knn_cross_work(int m, int n, int k);
+int svae_knn_cross(const double* Q, int ldq, int m, const double* X, int ldx, int n, int d, int k, void* work, int* idx, double* dist,
+                   void* stream);
 
 /* ------------------------------------------------------- t-SNE of the latents on their exact kNN graph (csrc/tsne.hip) --------- */
 /* sklearn's TSNE with an exact gradient, all fp64, no FMA contraction, every result bit-reproducible for a given (n, chunks).
@@ -758,6 +770,38 @@ int svae_tsne_repulsion(const double* Y, int n, int chunks, double* work, double
  * (no check this iteration).  update == NULL evaluates only: klpart and gradsq (of the plain gradient) at Y, nothing modified. */
 int svae_tsne_step(const int* rowptr, const int* col, const double* val, double exag, double* Y, const double* R, const double* Z,
                    double* update, double* gains, double momentum, double lr, int n, double* klpart, double* gradsq, void* stream);
+/* Placing new rows on a fitted map: every query is an optimisation of its own in the field of the n fixed map points.
+ *
+ * svae_tsne_cross_repulsion: for every query i < m of Yq [m][2] over ALL j < n of Yref [n][2] in ascending j (1 <= m, n <= 2^26),
+ * with d = yq_i - yref_j and q = 1.0 / (1.0 + (d0 d0 + d1 d1)):
+ *     R [m][2] = sum_j q q d        rowq [m] = sum_j q
+ * No exclusion by index (a query on top of a map point adds q = 1 and no force) and no global Z: a query normalises by its own
+ * rowq.  The kernel of svae_tsne_repulsion on a rectangle: one query per thread in registers, candidates broadcast from LDS, the
+ * columns split into `chunks` ranges of whole 64-column tiles whose partials are added in chunk order.  1 <= chunks <=
+ * SVAE_TSNE_MAX_CHUNKS is taken as given (at most one per tile).  chunks = 0 picks the split from n alone, never from m: the
+ * most there are, min(8, tiles), in ranges of ceil(tiles / that) tiles.  So the bits of a query's
+ * sums depend on (yq_i, Yref, n, chunks) only, not on the other queries of the launch or on m.  Yq and Yref must not overlap
+ * (SVAE_ERR_ARG).  work: svae_tsne_cross_repulsion_work doubles (0 for arguments out of range): chunks x 3 x m padded to 256.
+ *
+ * svae_tsne_place_step: one descent step of every query against the fixed map.  idx [m][k] int32 (entries in [0, n): the caller's
+ * guarantee) and P [m][k] fp64 are the query's reference neighbours and conditional probabilities, 1 <= k <= SVAE_KNN_MAX_K,
+ * 1 <= m <= 2^26; R and rowq come from svae_tsne_cross_repulsion at the same Yq.  Per query, over its entries in stored order with
+ * d = yq_i - yref_j, w = 1.0 + (d0 d0 + d1 d1) and p = exag P:
+ *     A = sum P (1.0 / w) d        klrow[i] = sum p log(p w) + log(rowq[i])        g = 2.0 (exag A - R[i] / rowq[i])
+ * (an entry with p = 0 adds nothing to klrow).  At exag = 1 klrow is the query's objective sum_e p log(p / q_e|i) with
+ * q_e|i = (1 / w) / rowq_i, and g its exact gradient (hence 2, not the 4 of the symmetric objective).  Then, in this order:
+ *     max_grad_norm > 0 and |g| = sqrt(g0 g0 + g1 g1) > max_grad_norm:  g = g (max_grad_norm / |g|)   (0: no clip)
+ *     gains = update g < 0 ? gains + 0.2 : gains 0.8, at least 0.01;   g = g gains
+ *     update = momentum update - lr g;   gradsq[i] = g . g;   Yq[i] = Yq[i] + update
+ * in one launch: a thread writes only its own row and reads only Yref besides.  klrow and gradsq may both be NULL.  update and
+ * gains go together; with both NULL only klrow and gradsq (of the clipped, ungained gradient) are evaluated and nothing moves.
+ * Everything NULL, or max_grad_norm < 0: SVAE_ERR_ARG. */
+long long svae_tsne_cross_repulsion_work(int m, int n, int chunks);
+int svae_tsne_cross_repulsion(const double* Yq, int m, const double* Yref, int n, int chunks, double* work, double* R, double* rowq,
+                              void* stream);
+int svae_tsne_place_step(const int* idx, const double* P, int k, double exag, double* Yq, const double* Yref, const double* R,
+                         const double* rowq, double* update, double* gains, double momentum, double lr, double max_grad_norm, int m,
+                         double* klrow, double* gradsq, void* stream);
 /* out[0] = sum of a [n], out[1] = sum of b [n] (b nullable): compensated sums at fixed positions, then a fixed tree */
 int svae_tsne_sums(const double* a, const double* b, long long n, double* out, void* stream);
 

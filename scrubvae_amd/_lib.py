@@ -211,6 +211,11 @@ SIGNATURES = {
     "svae_tsne_repulsion": (I, [P, I, I, P, P, P, P, P]),
     "svae_tsne_step": (I, [P, P, P, D, P, P, P, P, P, D, D, I, P, P, P]),
     "svae_tsne_sums": (I, [P, P, LL, P, P]),
+    "svae_knn_cross_work": (LL, [I, I, I]),
+    "svae_knn_cross": (I, [P, I, I, P, I, I, I, I, P, P, P, P]),
+    "svae_tsne_cross_repulsion_work": (LL, [I, I, I]),
+    "svae_tsne_cross_repulsion": (I, [P, I, P, I, I, P, P, P, P]),
+    "svae_tsne_place_step": (I, [P, P, I, D, P, P, P, P, P, P, D, D, D, I, P, P, P]),
     "svae_hsic_work": (LL, [I, I]),
     "svae_hsic_moments": (I, [P, I, I, P, I, P, P, P, P, P]),
     "svae_hsic_cross": (I, [P, I, I, I, P, P, I, P, P, P, I, P, P, P]),

@@ -10,7 +10,13 @@
 // distance arithmetic bounds the kernel.  At the end each block writes its rows' lists, sorted, to the work buffer, and
 // knn_finish_kernel merges the lists of the column chunks of a row by rank (a plain copy when there is one chunk) and takes the
 // square roots.
+//
+// svae_knn_cross is the same search for a query set Q against a database X (pair_tiles.h with a candidate matrix of its own): the
+// key runs over all rows of X, nothing is left out, and the column chunks are planned from the row tiles of Q and the column
+// tiles of X.
 #include "svae_internal.h"
+
+#include <algorithm>
 
 #include "knn_buffer.h"  // pair_tiles.h: the tile walk and #pragma clang fp contract(off)
 
@@ -71,6 +77,43 @@ __global__ __launch_bounds__(256) void knn_lists_kernel(const double* __restrict
   if (ok) buf.write_sorted(k, lane, wave, part_key + ((long long)blockIdx.y * rpad + r) * k, part_idx + ((long long)blockIdx.y * rpad + r) * k);
 }
 
+// The same walk for the m rows of Q against the n rows of X (svae_knn_cross): every column is a candidate, a query that equals a
+// reference row included, so there is no self or group test.  When d > 64 the rows restaged per tile come from Q (pair_rows).
+__global__ __launch_bounds__(256) void knn_cross_lists_kernel(const double* __restrict__ Q, int ldq, int m, const double* __restrict__ X,
+                                                              int ldx, int n, int d, int k, int ch, long long rpad,
+                                                              u64* __restrict__ part_key, int* __restrict__ part_idx) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  const KnnBuf buf(lds + N_KEY);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long long r0 = (long long)blockIdx.x * HR;
+  const long long r = r0 + lane;
+  const bool ok = r < m;
+  const int t_lo = (int)blockIdx.y * ch, t_hi = min(((int)blockIdx.y + 1) * ch, pair_tile_count(n));
+  const PairRows rows = pair_rows(Q, ldq, d, m, r0, lds + PAIR_LDS_QS, lds + PAIR_LDS_CS, X, ldx, n);
+  u64 thr = buf.reset(ok, lane);
+  for (int ct = t_lo; ct < t_hi; ++ct) {
+    const long long c0 = (long long)ct * HT;
+    double s[HQ];
+    pair_tile(rows, c0, s);  // its first barrier also ends the setup above and the previous tile's cut
+#pragma unroll
+    for (int q = 0; q < HQ; ++q) {
+      const u64 key = (u64)__double_as_longlong(s[q]);
+      if (key < thr) {
+        const long long c = c0 + wave * HQ + q;
+        if (c < n) buf.append(lane, key, (int)c);
+      }
+    }
+    __syncthreads();
+    if (buf.could_overflow(lane)) {
+      buf.cut(k, lane, wave);
+      thr = buf.ths[lane];
+    }
+  }
+  __syncthreads();
+  buf.cut(k, lane, wave);
+  if (ok) buf.write_sorted(k, lane, wave, part_key + ((long long)blockIdx.y * rpad + r) * k, part_idx + ((long long)blockIdx.y * rpad + r) * k);
+}
+
 // One thread per (row, position e): the entry at e of each chunk's list goes to its rank among all the chunks' entries of the row,
 // e plus the number of smaller keys in every other list (a binary search: the lists ascend, padding last).  Keys are unique, so
 // every rank below k is written exactly once when the row has at least k candidates.
@@ -127,5 +170,47 @@ extern "C" int svae_knn(const double* Z, int ld, int d, int n, int k, const int*
   const long long cells = (long long)n * k;
   hipLaunchKernelGGL(knn_finish_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, ST(stream), part_key, part_idx, (int)p.gy, p.rpad,
                      n, k, idx, dist);
+  return check_launch("knn_finish");
+}
+
+// knn_plan's rule with the row tiles counted from m and the column tiles from n
+static KnnPlan knn_cross_plan(int m, int n) {
+  KnnPlan p;
+  const int rt = pair_tile_count(m), ct = pair_tile_count(n);
+  p.gx = (unsigned)rt;
+  const long long per = (KNN_BLOCKS + (long long)rt - 1) / rt;
+  const int want = (int)std::min<long long>(per, std::min(KNN_NGY, ct));
+  p.ch = (ct + want - 1) / want;
+  p.gy = (unsigned)((ct + p.ch - 1) / p.ch);
+  p.rpad = (long long)rt * HR;
+  return p;
+}
+
+static bool knn_cross_sizes_ok(int m, int n, int k) { return m >= 1 && n >= 1 && k >= 1 && k <= SVAE_KNN_MAX_K && k <= n; }
+
+extern "C" long long svae_knn_cross_work(int m, int n, int k) {
+  if (!knn_cross_sizes_ok(m, n, k)) return 0;
+  const KnnPlan p = knn_cross_plan(m, n);
+  return (long long)p.gy * p.rpad * k * 12;
+}
+
+extern "C" int svae_knn_cross(const double* Q, int ldq, int m, const double* X, int ldx, int n, int d, int k, void* work, int* idx,
+                              double* dist, void* stream) {
+  if (int e = check_pair_rows("knn_cross (queries)", Q, ldq, d, m, 1)) return e;
+  if (int e = check_pair_rows("knn_cross (reference)", X, ldx, d, n, 1)) return e;
+  SVAE_REQUIRE(knn_cross_sizes_ok(m, n, k), SVAE_ERR_ARG, "knn_cross: bad neighbour count (k=%d n=%d, at most %d)", k, n, SVAE_KNN_MAX_K);
+  SVAE_REQUIRE(work && idx && dist, SVAE_ERR_ARG, "knn_cross: null argument");
+  SVAE_REQUIRE((reinterpret_cast<uintptr_t>(work) & 7u) == 0, SVAE_ERR_ALIGN, "knn_cross: work must be 8-byte aligned");
+  const KnnPlan p = knn_cross_plan(m, n);
+  u64* part_key = static_cast<u64*>(work);
+  int* part_idx = reinterpret_cast<int*>(part_key + (long long)p.gy * p.rpad * k);
+  static DeviceOnce once;
+  if (int e = allow_lds(knn_cross_lists_kernel, once, (int)KNN_LDS, "knn_cross")) return e;
+  hipLaunchKernelGGL(knn_cross_lists_kernel, dim3(p.gx, p.gy), dim3(256), KNN_LDS, ST(stream), Q, ldq, m, X, ldx, n, d, k, p.ch, p.rpad,
+                     part_key, part_idx);
+  if (int e = check_launch("knn_cross_lists")) return e;
+  const long long cells = (long long)m * k;
+  hipLaunchKernelGGL(knn_finish_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, ST(stream), part_key, part_idx, (int)p.gy, p.rpad,
+                     m, k, idx, dist);
   return check_launch("knn_finish");
 }

@@ -55,10 +55,13 @@ __device__ __forceinline__ void pair_accumulate(const double* qs, const double* 
   }
 }
 
-// This block's 64 rows [r0, r0 + 64) against the n rows of X: qs [HQCH * HD * HQLD] and cs [HT * HD] doubles of LDS
+// This block's 64 rows [r0, r0 + 64) of X [n] against the nc candidate rows of C (X itself unless a kernel searches one matrix
+// against another, as knn_cross_lists_kernel): qs [HQCH * HD * HQLD] and cs [HT * HD] doubles of LDS
 struct PairRows {
   const double* X;
   int ld, d, n, nch;  // nch feature chunks
+  const double* C;    // the candidates [nc][ldc], of the same d features
+  int ldc, nc;
   long long r0;
   bool resident;      // the rows stay in qs for the whole kernel; otherwise every tile restages them chunk by chunk
   double *qs, *cs;
@@ -66,7 +69,8 @@ struct PairRows {
 };
 
 // stages the rows for the whole kernel when they fit (visible after the first barrier of the first pair_tile)
-__device__ __forceinline__ PairRows pair_rows(const double* __restrict__ X, int ld, int d, int n, long long r0, double* qs, double* cs) {
+__device__ __forceinline__ PairRows pair_rows(const double* __restrict__ X, int ld, int d, int n, long long r0, double* qs, double* cs,
+                                              const double* __restrict__ C = nullptr, int ldc = 0, int nc = 0) {
   const int nch = (d + HD - 1) / HD;
   bool resident = false;
   if (nch <= HQCH) {
@@ -74,7 +78,8 @@ __device__ __forceinline__ PairRows pair_rows(const double* __restrict__ X, int 
     for (int ch = 0; ch < nch; ++ch) pair_stage_rows(X, ld, d, n, r0, ch * HD, qs + ch * HD * HQLD);
     resident = true;
   }
-  return PairRows{X, ld, d, n, nch, r0, resident, qs, cs, (int)(threadIdx.x & 63), (int)(threadIdx.x >> 6)};
+  if (!C) C = X, ldc = ld, nc = n;
+  return PairRows{X, ld, d, n, nch, C, ldc, nc, r0, resident, qs, cs, (int)(threadIdx.x & 63), (int)(threadIdx.x >> 6)};
 }
 
 // s[q] = the squared distance of row r0 + lane to candidate c0 + 16 wave + q.  Every thread of the block takes the two barriers
@@ -86,7 +91,7 @@ __device__ __forceinline__ void pair_tile(const PairRows& p, long long c0, doubl
   for (int ch = 0; ch < p.nch; ++ch) {
     __syncthreads();
     if (!p.resident) pair_stage_rows(p.X, p.ld, p.d, p.n, p.r0, ch * HD, p.qs);
-    pair_stage_cands(p.X, p.ld, p.d, p.n, c0, ch * HD, p.cs);
+    pair_stage_cands(p.C, p.ldc, p.d, p.nc, c0, ch * HD, p.cs);
     __syncthreads();
     if (live) pair_accumulate(p.resident ? p.qs + ch * HD * HQLD : p.qs, p.cs, p.lane, p.wave, s);
   }

@@ -6,6 +6,11 @@
 //                           (y0, y1) in registers and every lane reads the same candidate from LDS (a broadcast).
 //   tsne_step_kernel        per row the attraction and KL part over its CSR entries in stored order, gradient, gains, update;
 //   tsne_move_kernel        Y += update in a launch of its own, so that no row sees a neighbour's new position.
+// Placing new rows on a fitted map (scrubvae_amd/eval/embed_transform.py): every query is a 2-D optimisation of its own in the
+// field of the fixed map points.
+//   tsne_repulsion_kernel<true>   the same sums for m queries over all n map points, none left out: m x n pairs;
+//   tsne_place_kernel             per query the attraction to its k reference neighbours, its own KL term, the gradient with the
+//                                 query's own normaliser rowq, an optional clip of its norm, gains, update and the move.
 // Everything is fp64 with contraction off: each subtract, multiply, add and divide is rounded on its own, the division
 // correctly.  No floating-point atomics, no cross-lane sums whose order depends on the schedule: every result is bit-reproducible
 // for a given (n, chunks).
@@ -67,22 +72,27 @@ __global__ __launch_bounds__(TS_SR) void tsne_search_kernel(const double* __rest
   beta_out[r0 + lane] = beta;
 }
 
-// part[(y * 3 + c) * rpad + i]: the sums of row i over the columns [y ch 64, (y + 1) ch 64) in ascending j; c = 0, 1: q^2 d, 2: q
-__global__ __launch_bounds__(TS_ROWS) void tsne_repulsion_kernel(const double* __restrict__ Y, int n, int ch, long long rpad,
-                                                                 double* __restrict__ part) {
+// part[(y * 3 + c) * rpad + i]: the sums of row i over the columns [y ch 64, (y + 1) ch 64) in ascending j; c = 0, 1: q^2 d, 2: q.
+// CROSS: the rows are the m queries Y and the columns the nc points of Yc, none left out (svae_tsne_cross_repulsion); otherwise
+// the columns are Y's own rows and (Yc, nc) are not read.
+template <bool CROSS>
+__global__ __launch_bounds__(TS_ROWS) void tsne_repulsion_kernel(const double* __restrict__ Y, int n, const double* __restrict__ Yc, int nc,
+                                                                 int ch, long long rpad, double* __restrict__ part) {
   __shared__ double2 cs[TS_ROWS];
   const int i = (int)blockIdx.x * TS_ROWS + (int)threadIdx.x;  // < rpad <= 2^26 + 255
   const int ii = min(i, n - 1);
   const double yi0 = Y[2 * (long long)ii], yi1 = Y[2 * (long long)ii + 1];
-  const int c_lo = (int)std::min<long long>(n, (long long)blockIdx.y * ch * TS_CT);
-  const int c_hi = (int)std::min<long long>(n, ((long long)blockIdx.y + 1) * ch * TS_CT);
+  const double* __restrict__ C = CROSS ? Yc : Y;
+  const int cols = CROSS ? nc : n;
+  const int c_lo = (int)std::min<long long>(cols, (long long)blockIdx.y * ch * TS_CT);
+  const int c_hi = (int)std::min<long long>(cols, ((long long)blockIdx.y + 1) * ch * TS_CT);
   double r0 = 0.0, r1 = 0.0, sq = 0.0;
   for (int c0 = c_lo; c0 < c_hi; c0 += TS_ROWS) {
     const int cnt = min(TS_ROWS, c_hi - c0);
     __syncthreads();  // the previous stage's reads are done
     if ((int)threadIdx.x < cnt) {
       const long long j = c0 + (int)threadIdx.x;
-      cs[threadIdx.x] = make_double2(Y[2 * j], Y[2 * j + 1]);
+      cs[threadIdx.x] = make_double2(C[2 * j], C[2 * j + 1]);
     }
     __syncthreads();
     const int self = i - c0;  // the row's own position in this stage, if it is in it
@@ -91,7 +101,7 @@ __global__ __launch_bounds__(TS_ROWS) void tsne_repulsion_kernel(const double* _
       const double2 c = cs[t];
       const double d0 = yi0 - c.x, d1 = yi1 - c.y;
       double q = 1.0 / (1.0 + (d0 * d0 + d1 * d1));
-      q = t == self ? 0.0 : q;  // left out by index: adds +0 to the three sums
+      if (!CROSS) q = t == self ? 0.0 : q;  // left out by index: adds +0 to the three sums
       const double qq = q * q;
       r0 = r0 + qq * d0;
       r1 = r1 + qq * d1;
@@ -175,6 +185,61 @@ __global__ __launch_bounds__(256) void tsne_move_kernel(double* __restrict__ Y, 
   if (e < count) Y[e] = Y[e] + update[e];
 }
 
+// One query per thread against the fixed map: its k neighbours idx / P [m][k] in stored order, R and rowq from the cross
+// repulsion.  A thread reads Yref and its own row of everything else, and writes only its own row: the move needs no launch of
+// its own.
+__global__ __launch_bounds__(256) void tsne_place_kernel(const int* __restrict__ idx, const double* __restrict__ P, int k, double exag,
+                                                         double* __restrict__ Yq, const double* __restrict__ Yref,
+                                                         const double* __restrict__ R, const double* __restrict__ rowq,
+                                                         double* __restrict__ update, double* __restrict__ gains, double momentum, double lr,
+                                                         double max_grad_norm, int m, double* __restrict__ klrow,
+                                                         double* __restrict__ gradsq) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= m) return;
+  const double yi0 = Yq[2 * i], yi1 = Yq[2 * i + 1];
+  const bool want_kl = klrow != nullptr;
+  double a0 = 0.0, a1 = 0.0, kl = 0.0;
+  for (long long e = i * k, end = e + k; e < end; ++e) {
+    const long long j = idx[e];
+    const double v = P[e];
+    const double d0 = yi0 - Yref[2 * j], d1 = yi1 - Yref[2 * j + 1];
+    const double w = 1.0 + (d0 * d0 + d1 * d1);
+    const double pq = v * (1.0 / w);
+    a0 = a0 + pq * d0;
+    a1 = a1 + pq * d1;
+    if (want_kl) {
+      const double p = exag * v;
+      kl = kl + (p > 0.0 ? p * log(p * w) : 0.0);  // an entry that underflowed to 0 adds nothing, as its limit
+    }
+  }
+  const double zq = rowq[i];
+  double g[2] = {2.0 * (exag * a0 - R[2 * i] / zq), 2.0 * (exag * a1 - R[2 * i + 1] / zq)};
+  if (max_grad_norm > 0.0) {
+    const double norm = sqrt(g[0] * g[0] + g[1] * g[1]);
+    if (norm > max_grad_norm) {
+      const double s = max_grad_norm / norm;
+      g[0] = g[0] * s;
+      g[1] = g[1] * s;
+    }
+  }
+  if (update) {
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const double u = update[2 * i + c];
+      double gn = gains[2 * i + c];
+      gn = u * g[c] < 0.0 ? gn + 0.2 : gn * 0.8;
+      gn = fmax(gn, 0.01);
+      g[c] = g[c] * gn;
+      gains[2 * i + c] = gn;
+      const double un = momentum * u - lr * g[c];
+      update[2 * i + c] = un;
+      Yq[2 * i + c] = (c == 0 ? yi0 : yi1) + un;
+    }
+  }
+  if (want_kl) klrow[i] = kl + log(zq);
+  if (gradsq) gradsq[i] = g[0] * g[0] + g[1] * g[1];
+}
+
 }  // namespace svae
 
 using namespace svae;
@@ -219,7 +284,8 @@ extern "C" int svae_tsne_repulsion(const double* Y, int n, int chunks, double* w
   SVAE_REQUIRE(tsne_sizes_ok(n, chunks), SVAE_ERR_ARG, "tsne_repulsion: bad args (n=%d chunks=%d)", n, chunks);
   SVAE_REQUIRE(Y && work && R && rowq && Z, SVAE_ERR_ARG, "tsne_repulsion: null argument");
   const TsnePlan p = tsne_plan(n, chunks);
-  hipLaunchKernelGGL(tsne_repulsion_kernel, dim3(p.gx, p.gy), dim3(TS_ROWS), 0, ST(stream), Y, n, p.ch, p.rpad, work);
+  hipLaunchKernelGGL(tsne_repulsion_kernel<false>, dim3(p.gx, p.gy), dim3(TS_ROWS), 0, ST(stream), Y, n, (const double*)nullptr, 0, p.ch, p.rpad,
+                     work);
   if (int e = check_launch("tsne_repulsion")) return e;
   hipLaunchKernelGGL(tsne_repulsion_finish_kernel, dim3(p.gx), dim3(256), 0, ST(stream), work, (int)p.gy, p.rpad, n, R, rowq);
   if (int e = check_launch("tsne_repulsion_finish")) return e;
@@ -241,6 +307,53 @@ extern "C" int svae_tsne_step(const int* rowptr, const int* col, const double* v
   if (!update) return SVAE_OK;
   hipLaunchKernelGGL(tsne_move_kernel, dim3((unsigned)((2ll * n + 255) / 256)), dim3(256), 0, ST(stream), Y, update, 2ll * n);
   return check_launch("tsne_move");
+}
+
+static bool tsne_cross_sizes_ok(int m, int n, int chunks) {
+  return m >= 1 && m <= TS_NMAX && n >= 1 && n <= TS_NMAX && chunks >= 0 && chunks <= SVAE_TSNE_MAX_CHUNKS;
+}
+
+// The rows come from m, the column split from n alone: chunks = 0 takes the most chunks there are, min(8, tiles), whatever m is, so a
+// query's chunk boundaries, and with them its bits, do not depend on how many other queries share the launch.  (A rule that looked
+// at the grid would; and measured, a grid of 391 x 2 blocks keeps 3 waves per SIMD busy and runs at two thirds of the rate of a
+// full one, while the partials of 8 chunks cost 192 B per query next to n pairs.)
+static TsnePlan tsne_cross_plan(int m, int n, int chunks) {
+  TsnePlan p = tsne_plan(n, chunks > 0 ? chunks : SVAE_TSNE_MAX_CHUNKS);
+  p.gx = (unsigned)((m + TS_ROWS - 1) / TS_ROWS);
+  p.rpad = (long long)p.gx * TS_ROWS;
+  return p;
+}
+
+extern "C" long long svae_tsne_cross_repulsion_work(int m, int n, int chunks) {
+  if (!tsne_cross_sizes_ok(m, n, chunks)) return 0;
+  const TsnePlan p = tsne_cross_plan(m, n, chunks);
+  return (long long)p.gy * 3 * p.rpad;
+}
+
+extern "C" int svae_tsne_cross_repulsion(const double* Yq, int m, const double* Yref, int n, int chunks, double* work, double* R,
+                                         double* rowq, void* stream) {
+  SVAE_REQUIRE(tsne_cross_sizes_ok(m, n, chunks), SVAE_ERR_ARG, "tsne_cross_repulsion: bad args (m=%d n=%d chunks=%d)", m, n, chunks);
+  SVAE_REQUIRE(Yq && Yref && work && R && rowq, SVAE_ERR_ARG, "tsne_cross_repulsion: null argument");
+  const uintptr_t q0 = reinterpret_cast<uintptr_t>(Yq), r0 = reinterpret_cast<uintptr_t>(Yref);
+  SVAE_REQUIRE(q0 + 16ull * m <= r0 || r0 + 16ull * n <= q0, SVAE_ERR_ARG, "tsne_cross_repulsion: Yq and Yref overlap");
+  const TsnePlan p = tsne_cross_plan(m, n, chunks);
+  hipLaunchKernelGGL(tsne_repulsion_kernel<true>, dim3(p.gx, p.gy), dim3(TS_ROWS), 0, ST(stream), Yq, m, Yref, n, p.ch, p.rpad, work);
+  if (int e = check_launch("tsne_cross_repulsion")) return e;
+  hipLaunchKernelGGL(tsne_repulsion_finish_kernel, dim3(p.gx), dim3(256), 0, ST(stream), work, (int)p.gy, p.rpad, m, R, rowq);
+  return check_launch("tsne_cross_repulsion_finish");
+}
+
+extern "C" int svae_tsne_place_step(const int* idx, const double* P, int k, double exag, double* Yq, const double* Yref, const double* R,
+                                    const double* rowq, double* update, double* gains, double momentum, double lr, double max_grad_norm,
+                                    int m, double* klrow, double* gradsq, void* stream) {
+  SVAE_REQUIRE(m >= 1 && m <= TS_NMAX && k >= 1 && k <= SVAE_KNN_MAX_K, SVAE_ERR_ARG, "tsne_place_step: bad sizes (m=%d k=%d)", m, k);
+  SVAE_REQUIRE(idx && P && Yq && Yref && R && rowq, SVAE_ERR_ARG, "tsne_place_step: null argument");
+  SVAE_REQUIRE((update != nullptr) == (gains != nullptr), SVAE_ERR_ARG, "tsne_place_step: update and gains go together");
+  SVAE_REQUIRE(update || klrow || gradsq, SVAE_ERR_ARG, "tsne_place_step: nothing to do");
+  SVAE_REQUIRE(max_grad_norm >= 0.0, SVAE_ERR_ARG, "tsne_place_step: max_grad_norm must be >= 0 (0: no clip), got %g", max_grad_norm);
+  hipLaunchKernelGGL(tsne_place_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ST(stream), idx, P, k, exag, Yq, Yref, R, rowq, update,
+                     gains, momentum, lr, max_grad_norm, m, klrow, gradsq);
+  return check_launch("tsne_place_step");
 }
 
 extern "C" int svae_tsne_sums(const double* a, const double* b, long long n, double* out, void* stream) {

@@ -1,6 +1,7 @@
 from .cluster import GaussianMixture, dbscan, gmm  # noqa: F401
 from .density import DensityGrid, DensityMap, density_map, density_regions  # noqa: F401
 from .embed import TSNE, tsne, tsne_affinities  # noqa: F401
+from .embed_transform import TSNEMap, tsne_transform  # noqa: F401
 from .embed_quality import EmbeddingQuality, continuity, embedding_quality, neighbor_ranks, trustworthiness  # noqa: F401
 from .eval import generative_restrictiveness  # noqa: F401
 from .hdbscan import HDBSCAN  # noqa: F401
@@ -9,5 +10,5 @@ from .metrics import (cluster_entropy, hungarian_match, knn_class_rand_cv, knn_r
                       log_class_rand_cv, mlp_rand_cv, mmd_bandwidth, mmd_estimate, mmd_permutation_test, mmd_permutations,
                       qda_rand_cv, shannon_entropy)
 from .mutual_info import MIPermutationResult, latent_mi_scores, mutual_information, mutual_information_permutation_test  # noqa: F401
-from .neighbors import kneighbors, kneighbors_graph, knn_label_purity  # noqa: F401
+from .neighbors import kneighbors, kneighbors_cross, kneighbors_graph, knn_label_purity, knn_transfer_labels  # noqa: F401
 from .silhouette import cluster_medoids, cluster_silhouette, silhouette_samples, silhouette_score  # noqa: F401
