@@ -170,11 +170,10 @@ static DenPlan den_plan(int n, int gx, int gy) {
   DenPlan p;
   p.tx = (unsigned)((gx + DEN_T - 1) / DEN_T);
   p.ty = (unsigned)((gy + DEN_T - 1) / DEN_T);
-  const int tiles = (int)(p.tx * p.ty);
   const int nchunks = (int)(((long long)n + DEN_CHUNK - 1) / DEN_CHUNK);
-  const int want = std::min(std::min(nchunks, DEN_MAX_SLICES), (DEN_BLOCKS + tiles - 1) / tiles);
-  p.cps = (nchunks + want - 1) / want;
-  p.slices = (unsigned)((nchunks + p.cps - 1) / p.cps);
+  const ChunkSplit s = chunk_split(nchunks, (long long)p.tx * p.ty, DEN_MAX_SLICES, DEN_BLOCKS);
+  p.cps = s.per;
+  p.slices = (unsigned)s.parts;
   return p;
 }
 

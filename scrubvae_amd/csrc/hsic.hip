@@ -58,14 +58,14 @@ __global__ __launch_bounds__(256) void hsic_moments_kernel(const double* __restr
   __shared__ __attribute__((aligned(16))) double qs[LAB ? 1 : HQCH * HD * HQLD];
   __shared__ __attribute__((aligned(16))) double cs[LAB ? 1 : HT * HD];
   __shared__ double red[2 * 256];
-  const long long r0 = (long long)blockIdx.x * HR;
-  const int t_lo = (int)blockIdx.y * ch, t_hi = min(((int)blockIdx.y + 1) * ch, pair_tile_count(n));
+  const PairTileRange tr = pair_chunk_tiles(n, ch);
+  const long long r0 = tr.r0;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long i = r0 + lane;
   double a1 = 0.0, a2 = 0.0;
   if constexpr (LAB) {
     const int li = i < n ? lab[i] : 0;
-    for (int ct = t_lo; ct < t_hi; ++ct) {
+    for (int ct = tr.t_lo; ct < tr.t_hi; ++ct) {
       const long long c0 = (long long)ct * HT + wave * HQ;
 #pragma unroll
       for (int q = 0; q < HQ; ++q) {
@@ -80,7 +80,7 @@ __global__ __launch_bounds__(256) void hsic_moments_kernel(const double* __restr
   } else {
     const double h = hp[0];
     const PairRows rows = pair_rows(X, ld, d, n, r0, qs, cs);
-    for (int ct = t_lo; ct < t_hi; ++ct) {
+    for (int ct = tr.t_lo; ct < tr.t_hi; ++ct) {
       const long long c0 = (long long)ct * HT;
       double s[HQ];
       pair_tile(rows, c0, s);

@@ -16,8 +16,6 @@
 // tiles of X.
 #include "svae_internal.h"
 
-#include <algorithm>
-
 #include "knn_buffer.h"  // pair_tiles.h: the tile walk and #pragma clang fp contract(off)
 
 namespace svae {
@@ -128,12 +126,7 @@ __global__ __launch_bounds__(256) void knn_finish_kernel(const u64* __restrict__
     const u64 k0 = part_key[base + e];
     const int j0 = part_idx[base + e];
     if (j0 == KNN_PAD) continue;
-    int rank = e;
-    for (int y2 = 0; y2 < gy && rank < k; ++y2) {
-      if (y2 == y) continue;
-      const long long b2 = ((long long)y2 * rpad + row) * k;
-      rank += knn_count_below(part_key, part_idx, b2, k, k0, j0);
-    }
+    const int rank = knn_merged_rank(part_key, part_idx, gy, rpad, row, k, y, e, k0, j0, k);
     if (rank < k) {
       idx[row * k + rank] = j0;
       dist[row * k + rank] = sqrt(__longlong_as_double((long long)k0));
@@ -145,53 +138,42 @@ __global__ __launch_bounds__(256) void knn_finish_kernel(const u64* __restrict__
 
 using namespace svae;
 
-static KnnPlan knn_plan(int n) { return knn_plan(n, KNN_NGY, KNN_BLOCKS); }
+// the row tiles counted from the m searching rows and the column tiles from the n searched ones
+static KnnPlan knn_plan(int m, int n) { return knn_plan(m, n, KNN_NGY, KNN_BLOCKS); }
+
+static int knn_finish(const KnnPlan& p, const KnnLists& l, int rows, int k, int* idx, double* dist, void* stream) {
+  const long long cells = (long long)rows * k;
+  hipLaunchKernelGGL(knn_finish_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, ST(stream), l.key, l.idx, (int)p.gy, p.rpad,
+                     rows, k, idx, dist);
+  return check_launch("knn_finish");
+}
 
 static bool knn_sizes_ok(int n, int k) { return n >= 2 && k >= 1 && k <= SVAE_KNN_MAX_K && k <= n - 1; }
 
 extern "C" long long svae_knn_work(int n, int k) {
   if (!knn_sizes_ok(n, k)) return 0;
-  const KnnPlan p = knn_plan(n);
-  return (long long)p.gy * p.rpad * k * 12;
+  return knn_work_bytes(knn_plan(n, n), k);
 }
 
 extern "C" int svae_knn(const double* Z, int ld, int d, int n, int k, const int* group, void* work, int* idx, double* dist, void* stream) {
   if (int e = check_pair_rows("knn", Z, ld, d, n, 2)) return e;
   SVAE_REQUIRE(knn_sizes_ok(n, k), SVAE_ERR_ARG, "knn: bad neighbour count (k=%d n=%d, at most %d)", k, n, SVAE_KNN_MAX_K);
   SVAE_REQUIRE(work && idx && dist, SVAE_ERR_ARG, "knn: null argument");
-  SVAE_REQUIRE((reinterpret_cast<uintptr_t>(work) & 7u) == 0, SVAE_ERR_ALIGN, "knn: work must be 8-byte aligned");
-  const KnnPlan p = knn_plan(n);
-  u64* part_key = static_cast<u64*>(work);
-  int* part_idx = reinterpret_cast<int*>(part_key + (long long)p.gy * p.rpad * k);
+  const KnnPlan p = knn_plan(n, n);
+  KnnLists l;
+  if (int e = knn_work_lists("knn", work, p, k, &l)) return e;
   static DeviceOnce once;
   if (int e = allow_lds(knn_lists_kernel, once, (int)KNN_LDS, "knn")) return e;
-  hipLaunchKernelGGL(knn_lists_kernel, dim3(p.gx, p.gy), dim3(256), KNN_LDS, ST(stream), Z, ld, d, n, k, group, p.ch, p.rpad, part_key, part_idx);
+  hipLaunchKernelGGL(knn_lists_kernel, dim3(p.gx, p.gy), dim3(256), KNN_LDS, ST(stream), Z, ld, d, n, k, group, p.ch, p.rpad, l.key, l.idx);
   if (int e = check_launch("knn_lists")) return e;
-  const long long cells = (long long)n * k;
-  hipLaunchKernelGGL(knn_finish_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, ST(stream), part_key, part_idx, (int)p.gy, p.rpad,
-                     n, k, idx, dist);
-  return check_launch("knn_finish");
-}
-
-// knn_plan's rule with the row tiles counted from m and the column tiles from n
-static KnnPlan knn_cross_plan(int m, int n) {
-  KnnPlan p;
-  const int rt = pair_tile_count(m), ct = pair_tile_count(n);
-  p.gx = (unsigned)rt;
-  const long long per = (KNN_BLOCKS + (long long)rt - 1) / rt;
-  const int want = (int)std::min<long long>(per, std::min(KNN_NGY, ct));
-  p.ch = (ct + want - 1) / want;
-  p.gy = (unsigned)((ct + p.ch - 1) / p.ch);
-  p.rpad = (long long)rt * HR;
-  return p;
+  return knn_finish(p, l, n, k, idx, dist, stream);
 }
 
 static bool knn_cross_sizes_ok(int m, int n, int k) { return m >= 1 && n >= 1 && k >= 1 && k <= SVAE_KNN_MAX_K && k <= n; }
 
 extern "C" long long svae_knn_cross_work(int m, int n, int k) {
   if (!knn_cross_sizes_ok(m, n, k)) return 0;
-  const KnnPlan p = knn_cross_plan(m, n);
-  return (long long)p.gy * p.rpad * k * 12;
+  return knn_work_bytes(knn_plan(m, n), k);
 }
 
 extern "C" int svae_knn_cross(const double* Q, int ldq, int m, const double* X, int ldx, int n, int d, int k, void* work, int* idx,
@@ -200,17 +182,13 @@ extern "C" int svae_knn_cross(const double* Q, int ldq, int m, const double* X, 
   if (int e = check_pair_rows("knn_cross (reference)", X, ldx, d, n, 1)) return e;
   SVAE_REQUIRE(knn_cross_sizes_ok(m, n, k), SVAE_ERR_ARG, "knn_cross: bad neighbour count (k=%d n=%d, at most %d)", k, n, SVAE_KNN_MAX_K);
   SVAE_REQUIRE(work && idx && dist, SVAE_ERR_ARG, "knn_cross: null argument");
-  SVAE_REQUIRE((reinterpret_cast<uintptr_t>(work) & 7u) == 0, SVAE_ERR_ALIGN, "knn_cross: work must be 8-byte aligned");
-  const KnnPlan p = knn_cross_plan(m, n);
-  u64* part_key = static_cast<u64*>(work);
-  int* part_idx = reinterpret_cast<int*>(part_key + (long long)p.gy * p.rpad * k);
+  const KnnPlan p = knn_plan(m, n);
+  KnnLists l;
+  if (int e = knn_work_lists("knn_cross", work, p, k, &l)) return e;
   static DeviceOnce once;
   if (int e = allow_lds(knn_cross_lists_kernel, once, (int)KNN_LDS, "knn_cross")) return e;
-  hipLaunchKernelGGL(knn_cross_lists_kernel, dim3(p.gx, p.gy), dim3(256), KNN_LDS, ST(stream), Q, ldq, m, X, ldx, n, d, k, p.ch, p.rpad,
-                     part_key, part_idx);
+  hipLaunchKernelGGL(knn_cross_lists_kernel, dim3(p.gx, p.gy), dim3(256), KNN_LDS, ST(stream), Q, ldq, m, X, ldx, n, d, k, p.ch, p.rpad, l.key,
+                     l.idx);
   if (int e = check_launch("knn_cross_lists")) return e;
-  const long long cells = (long long)m * k;
-  hipLaunchKernelGGL(knn_finish_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, ST(stream), part_key, part_idx, (int)p.gy, p.rpad,
-                     m, k, idx, dist);
-  return check_launch("knn_finish");
+  return knn_finish(p, l, m, k, idx, dist, stream);
 }

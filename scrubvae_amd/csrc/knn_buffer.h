@@ -1,6 +1,7 @@
-// The running best k of 64 rows in LDS, the shared layer of knn.hip and mi.hip: a block of 256 threads (lane = row, the same rows
-// in each of the 4 waves, as in pair_tiles.h) walks its column tiles in ascending order and keeps, for every row, the k smallest
-// keys (s, j) seen so far: s a non-negative double compared by its bit pattern, then the lower j.
+// The running best k of 64 rows in LDS, the shared layer of knn.hip and mi.hip (rank.hip takes the key order, the plan and
+// knn_count_below from here): a block of 256 threads (lane = row, the same rows in each of the 4 waves, as in pair_tiles.h) walks
+// its column tiles in ascending order and keeps, for every row, the k smallest keys (s, j) seen so far: s a non-negative double
+// compared by its bit pattern, then the lower j.  Below the buffer: the merge of the column chunks' lists, their plan and layout.
 //
 // Every row has a buffer of CAP candidates, entry-major (entry e of row r at [e * 64 + r]: conflict-free for the lanes of a wave),
 // filled through a per-row LDS counter because the four waves see different candidates of the same row.  Each lane holds the s of
@@ -13,6 +14,7 @@
 #include <climits>
 
 #include "pair_tiles.h"
+#include "svae_internal.h"  // chunk_split, SVAE_REQUIRE
 
 namespace svae {
 
@@ -130,24 +132,46 @@ __device__ __forceinline__ int knn_count_below(const u64* __restrict__ part_key,
   return lo;
 }
 
-// The column-chunk plan that knn.hip and mi.hip share: grid y splits the column tiles (at most ngy chunks) only while the grid
-// holds fewer than `blocks` blocks
+// The merge of a row's gy lists by rank: the entry (k0, j0) at position e of chunk y's list has the rank e plus the number of
+// smaller keys in every other list (the keys are unique).  Exact below `limit`; once the rank reaches it, some value >= limit.
+__device__ __forceinline__ int knn_merged_rank(const u64* __restrict__ part_key, const int* __restrict__ part_idx, int gy, long long rpad,
+                                               long long row, int k, int y, int e, u64 k0, int j0, int limit) {
+  int rank = e;
+  for (int y2 = 0; y2 < gy && rank < limit; ++y2) {
+    if (y2 == y) continue;
+    rank += knn_count_below(part_key, part_idx, ((long long)y2 * rpad + row) * k, k, k0, j0);
+  }
+  return rank;
+}
+
+// The column-chunk plan of a walk over rows x cols pairs: grid x the row tiles, grid y the chunks of chunk_split (svae_internal.h)
+// over the column tiles, at most ngy of them
 struct KnnPlan {
   int ch;
   unsigned gx, gy;
   long long rpad;
 };
 
-inline KnnPlan knn_plan(int n, int ngy, int blocks) {
-  KnnPlan p;
-  const int nt = pair_tile_count(n);
-  p.gx = (unsigned)nt;
-  const long long per = (blocks + (long long)nt - 1) / nt;
-  const int want = (int)(per < ngy ? (per < nt ? per : nt) : (ngy < nt ? ngy : nt));
-  p.ch = (nt + want - 1) / want;
-  p.gy = (unsigned)((nt + p.ch - 1) / p.ch);
-  p.rpad = (long long)nt * HR;
-  return p;
+inline KnnPlan knn_plan(int rows, int cols, int ngy, int blocks) {
+  const int rt = pair_tile_count(rows);
+  const ChunkSplit s = chunk_split(pair_tile_count(cols), rt, ngy, blocks);
+  return KnnPlan{s.per, (unsigned)rt, (unsigned)s.parts, (long long)rt * HR};
+}
+inline KnnPlan knn_plan(int n, int ngy, int blocks) { return knn_plan(n, n, ngy, blocks); }
+
+// The lists of a plan in the caller's work buffer: part_key [gy][rpad][k] uint64, then part_idx [gy][rpad][k] int32
+inline long long knn_work_bytes(const KnnPlan& p, int k) {
+  return (long long)p.gy * p.rpad * k * (long long)(sizeof(u64) + sizeof(int));
+}
+struct KnnLists {
+  u64* key;
+  int* idx;
+};
+inline int knn_work_lists(const char* what, void* work, const KnnPlan& p, int k, KnnLists* l) {
+  SVAE_REQUIRE((reinterpret_cast<uintptr_t>(work) & 7u) == 0, SVAE_ERR_ALIGN, "%s: work must be 8-byte aligned", what);
+  l->key = static_cast<u64*>(work);
+  l->idx = reinterpret_cast<int*>(l->key + (long long)p.gy * p.rpad * k);
+  return SVAE_OK;
 }
 
 }  // namespace svae

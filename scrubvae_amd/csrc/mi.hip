@@ -120,9 +120,9 @@ __global__ __launch_bounds__(256) void mi_radius_kernel(const double* __restrict
   if (ok) buf.write_sorted(k, lane, wave, part_key + ((long long)blockIdx.y * rpad + r) * k, part_idx + ((long long)blockIdx.y * rpad + r) * k);
 }
 
-// One thread per (row, position e): the rank of the entry at e of each chunk's list among all the chunks' entries of the row is e
-// plus the number of smaller keys in every other list.  Keys are unique, so exactly one entry has the rank k - 1 (kk[row] - 1
-// with labels) when the row has that many candidates: its s is rho2.
+// One thread per (row, position e), ranking the entry at e of each chunk's list among all the chunks' entries of the row
+// (knn_merged_rank).  Keys are unique, so exactly one entry has the rank k - 1 (kk[row] - 1 with labels) when the row has that
+// many candidates: its s is rho2.
 __global__ __launch_bounds__(256) void mi_finish_kernel(const u64* __restrict__ part_key, const int* __restrict__ part_idx, int gy,
                                                         long long rpad, int n, int k, const int* __restrict__ kk, double* __restrict__ rho2) {
   const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -135,11 +135,7 @@ __global__ __launch_bounds__(256) void mi_finish_kernel(const u64* __restrict__ 
     const u64 k0 = part_key[base + e];
     const int j0 = part_idx[base + e];
     if (j0 == KNN_PAD) continue;
-    int rank = e;
-    for (int y2 = 0; y2 < gy && rank <= want; ++y2) {
-      if (y2 == y) continue;
-      rank += knn_count_below(part_key, part_idx, ((long long)y2 * rpad + row) * k, k, k0, j0);
-    }
+    const int rank = knn_merged_rank(part_key, part_idx, gy, rpad, row, k, y, e, k0, j0, want + 1);
     if (rank == want) rho2[row] = __longlong_as_double((long long)k0);
   }
 }
@@ -153,10 +149,9 @@ __global__ __launch_bounds__(256) void mi_count_kernel(const double* __restrict_
   double* cy = lds + MI_Y;
   int* cnt = reinterpret_cast<int*>(lds + MI_CNT);  // [which][wave][lane]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const long long r0 = (long long)blockIdx.x * HR;
-  const long long r = r0 + lane;
+  const PairTileRange tr = pair_chunk_tiles(n, ch);
+  const long long r = tr.r0 + lane;
   const bool ok = r < n;
-  const int t_lo = (int)blockIdx.y * ch, t_hi = min(((int)blockIdx.y + 1) * ch, pair_tile_count(n));
   const u64 rb = ok ? (u64)__double_as_longlong(rho2[r]) : 0ull;  // a lane past n counts nothing
   double my[SVAE_MI_MAX_Y] = {0.0, 0.0, 0.0, 0.0};
   if (REAL) {
@@ -164,9 +159,9 @@ __global__ __launch_bounds__(256) void mi_count_kernel(const double* __restrict_
     for (int f = 0; f < SVAE_MI_MAX_Y; ++f)
       if (ok && f < q) my[f] = Y[r * q + f];
   }
-  const PairRows rows = pair_rows(Z, ld, d, n, r0, lds + PAIR_LDS_QS, lds + PAIR_LDS_CS);
+  const PairRows rows = pair_rows(Z, ld, d, n, tr.r0, lds + PAIR_LDS_QS, lds + PAIR_LDS_CS);
   int az = 0, ay = 0;
-  for (int ct = t_lo; ct < t_hi; ++ct) {
+  for (int ct = tr.t_lo; ct < tr.t_hi; ++ct) {
     const long long c0 = (long long)ct * HT;
     if (REAL) mi_stage_y(Y, q, n, c0, cy);
     double s[HQ];
@@ -225,8 +220,7 @@ static bool mi_sizes_ok(int n, int k) { return n >= 2 && k >= 1 && k <= SVAE_MI_
 
 extern "C" long long svae_mi_work(int n, int k) {
   if (!mi_sizes_ok(n, k)) return 0;
-  const KnnPlan p = mi_plan(n);
-  return (long long)p.gy * p.rpad * k * 12;
+  return knn_work_bytes(mi_plan(n), k);
 }
 
 // the checks that svae_mi_radius and svae_mi_counts share
@@ -243,24 +237,23 @@ extern "C" int svae_mi_radius(const double* Z, int ld, int d, int n, const doubl
   SVAE_REQUIRE(mi_sizes_ok(n, k), SVAE_ERR_ARG, "mi_radius: bad neighbour count (k=%d n=%d, at most %d)", k, n, SVAE_MI_MAX_K);
   SVAE_REQUIRE((kk != nullptr) == (lab != nullptr), SVAE_ERR_ARG, "mi_radius: kk belongs to the labels");
   SVAE_REQUIRE(work && rho2, SVAE_ERR_ARG, "mi_radius: null argument");
-  SVAE_REQUIRE((reinterpret_cast<uintptr_t>(work) & 7u) == 0, SVAE_ERR_ALIGN, "mi_radius: work must be 8-byte aligned");
   const KnnPlan p = mi_plan(n);
-  u64* part_key = static_cast<u64*>(work);
-  int* part_idx = reinterpret_cast<int*>(part_key + (long long)p.gy * p.rpad * k);
+  KnnLists l;
+  if (int e = knn_work_lists("mi_radius", work, p, k, &l)) return e;
   if (lab) {
     static DeviceOnce once;
     if (int e = allow_lds(mi_radius_kernel<true>, once, (int)MI_RADIUS_LDS, "mi_radius")) return e;
     hipLaunchKernelGGL(mi_radius_kernel<true>, dim3(p.gx, p.gy), dim3(256), MI_RADIUS_LDS, ST(stream), Z, ld, d, n, Y, q, lab, kk, k, p.ch,
-                       p.rpad, part_key, part_idx);
+                       p.rpad, l.key, l.idx);
   } else {
     static DeviceOnce once;
     if (int e = allow_lds(mi_radius_kernel<false>, once, (int)MI_RADIUS_LDS, "mi_radius")) return e;
     hipLaunchKernelGGL(mi_radius_kernel<false>, dim3(p.gx, p.gy), dim3(256), MI_RADIUS_LDS, ST(stream), Z, ld, d, n, Y, q, lab, kk, k, p.ch,
-                       p.rpad, part_key, part_idx);
+                       p.rpad, l.key, l.idx);
   }
   if (int e = check_launch("mi_radius")) return e;
   const long long cells = (long long)n * k;
-  hipLaunchKernelGGL(mi_finish_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, ST(stream), part_key, part_idx, (int)p.gy, p.rpad,
+  hipLaunchKernelGGL(mi_finish_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, ST(stream), l.key, l.idx, (int)p.gy, p.rpad,
                      n, k, kk, rho2);
   return check_launch("mi_finish");
 }

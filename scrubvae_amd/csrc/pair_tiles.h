@@ -1,6 +1,7 @@
 // All-pairs squared distances of fp64 rows in 64 x 64 tiles, the shared layer of hdbscan.hip, mmd.hip, mmd_null.hip,
-// silhouette.hip, knn.hip and hsic.hip: a block of 256 threads holds 64 rows (lane = row, the same rows in each of the 4 waves) against 64 candidates
-// (wave w takes candidates [16 w, 16 w + 16)), both staged through LDS 16 features at a time.
+// silhouette.hip, hsic.hip and, through knn_buffer.h, knn.hip, mi.hip and rank.hip: a block of 256 threads holds 64 rows (lane =
+// row, the same rows in each of the 4 waves) against 64 candidates (wave w takes candidates [16 w, 16 w + 16)), both staged
+// through LDS 16 features at a time.  (density.hip takes only double4_t and the matrix-core lane layout from here.)
 // s = ((x0 - y0)^2 + (x1 - y1)^2) + ... in feature order, every subtract, multiply and add rounded on its own: the pragma below
 // is part of the contract.  A kernel builds its block's rows once (pair_rows) and asks for one tile of s at a time (pair_tile).
 #pragma once
@@ -97,11 +98,15 @@ __device__ __forceinline__ void pair_tile(const PairRows& p, long long c0, doubl
   }
 }
 
-// Upper triangle i < j: block (x, y) takes row tile x against the column tiles [y ch, (y + 1) ch) on or above the diagonal
+// Block (x, y) takes row tile x against the column tiles [y ch, (y + 1) ch) of the n_cols candidates
 struct PairTileRange {
   long long r0;
   int t_lo, t_hi;  // column tiles [t_lo, t_hi); empty (block-uniform) when t_lo >= t_hi
 };
+__device__ __forceinline__ PairTileRange pair_chunk_tiles(int n_cols, int ch) {
+  return PairTileRange{(long long)blockIdx.x * HR, (int)blockIdx.y * ch, min(((int)blockIdx.y + 1) * ch, pair_tile_count(n_cols))};
+}
+// Upper triangle i < j: of that chunk, the tiles on or above the diagonal
 __device__ __forceinline__ PairTileRange pair_upper_tiles(int n, int ch) {
   PairTileRange t;
   t.r0 = (long long)blockIdx.x * HR;

@@ -85,10 +85,10 @@ __global__ __launch_bounds__(256) void rank_count_kernel(const double* __restric
   int* tidx = reinterpret_cast<int*>(lds + R_KEY + k * HR);
   unsigned* hist = reinterpret_cast<unsigned*>(lds + R_KEY + k * HR + k * HR / 2);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const long long r0 = (long long)blockIdx.x * HR;
+  const PairTileRange tr = pair_chunk_tiles(n, ch);
+  const long long r0 = tr.r0;
   const long long r = r0 + lane;
   const bool ok = r < n;
-  const int t_lo = (int)blockIdx.y * ch, t_hi = min(((int)blockIdx.y + 1) * ch, pair_tile_count(n));
   // a row past n holds thresholds below every candidate, so its lanes count nothing
   for (int e = threadIdx.x; e < k * HR; e += 256) {
     const int p = e >> 6;
@@ -100,7 +100,7 @@ __global__ __launch_bounds__(256) void rank_count_kernel(const double* __restric
   const u64 top_key = ok ? thr_key[r * k + k - 1] : 0ull;  // the row's largest threshold
   const int top_idx = ok ? thr_idx[r * k + k - 1] : -1;
   const PairRows rows = pair_rows(X, ld, d, n, r0, lds + PAIR_LDS_QS, lds + PAIR_LDS_CS);
-  for (int ct = t_lo; ct < t_hi; ++ct) {
+  for (int ct = tr.t_lo; ct < tr.t_hi; ++ct) {
     const long long c0 = (long long)ct * HT;
     double s[HQ];
     pair_tile(rows, c0, s);  // its first barrier also ends the setup above

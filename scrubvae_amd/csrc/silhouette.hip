@@ -36,8 +36,8 @@ __global__ __launch_bounds__(256) void sil_sums_kernel(const double* __restrict_
   extern __shared__ __attribute__((aligned(16))) double lds[];
   double* kt = lds + PAIR_LDS_KT;
   int* lb = reinterpret_cast<int*>(lds + S_LB);
-  const long long r0 = (long long)row0 + (long long)blockIdx.x * HR;
-  const int t_lo = (int)blockIdx.y * ch, t_hi = min(((int)blockIdx.y + 1) * ch, pair_tile_count(n));
+  const PairTileRange tr = pair_chunk_tiles(n, ch);
+  const long long r0 = (long long)row0 + tr.r0;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int l16 = lane & 15, kg = lane >> 4;
   const int cbase = (int)blockIdx.z * NC + l16;  // this lane's column of result tile 0
@@ -45,7 +45,7 @@ __global__ __launch_bounds__(256) void sil_sums_kernel(const double* __restrict_
   double4_t acc[NT];
 #pragma unroll
   for (int t = 0; t < NT; ++t) acc[t] = double4_t{0.0, 0.0, 0.0, 0.0};
-  for (int ct = t_lo; ct < t_hi; ++ct) {
+  for (int ct = tr.t_lo; ct < tr.t_hi; ++ct) {
     const long long c0 = (long long)ct * HT;
     double s[HQ];
     pair_tile(rows, c0, s);  // its first barrier also ends the previous tile's reads of kt and lb
@@ -158,11 +158,9 @@ static SilPlan sil_plan(int rows, int n, int K) {
   p.nc = K <= 16 ? 16 : K <= 64 ? 64 : 256;
   p.gz = (unsigned)((K + p.nc - 1) / p.nc);
   p.gx = (unsigned)pair_tile_count(rows);
-  const int nt = pair_tile_count(n);
-  const long long xz = (long long)p.gx * p.gz;
-  const int want = (int)std::min<long long>(std::min(nt, SIL_NGY), (SIL_BLOCKS + xz - 1) / xz);
-  p.ch = (nt + want - 1) / want;
-  p.gy = (unsigned)((nt + p.ch - 1) / p.ch);
+  const ChunkSplit s = chunk_split(pair_tile_count(n), (long long)p.gx * p.gz, SIL_NGY, SIL_BLOCKS);
+  p.ch = s.per;
+  p.gy = (unsigned)s.parts;
   p.rpad = (long long)p.gx * HR;
   p.kpad = (int)p.gz * p.nc;
   return p;

@@ -1,6 +1,7 @@
 // Internal helpers shared by the HIP translation units of libscrubvae_hip.so.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <climits>
 #include <cstdarg>
 #include <cstdio>
@@ -62,6 +63,22 @@ inline int allow_lds(K kernel, DeviceOnce& once, int bytes, const char* what) {
 inline int check_pair_rows(const char* what, const double* X, int ld, int d, int n, int n_min, int n_max = INT_MAX) {
   SVAE_REQUIRE(X && n >= n_min && n <= n_max && d >= 1 && ld >= d, SVAE_ERR_ARG, "%s: bad rows (n=%d d=%d ld=%d)", what, n, d, ld);
   return SVAE_OK;
+}
+
+// How the kernels that split their inner units (column tiles, point chunks) over a grid dimension split them: into `want` parts
+// of `per` units, of which `parts` are not empty.  chunk_split asks for as many parts as there are units, at most `cap`, and only
+// while the `row_blocks` blocks of the other grid dimensions leave the grid below `blocks` blocks.  Where partial fp64 sums are
+// added per part, this rule fixes their order: it is a function of the sizes alone, never of the device.
+struct ChunkSplit {
+  int per, parts;
+};
+// the two ceilings alone, for a caller that was told `want` (t-SNE's chunks > 0); every other plan goes through chunk_split
+inline ChunkSplit chunk_split_into(int units, int want) {
+  const int per = (units + want - 1) / want;
+  return ChunkSplit{per, (units + per - 1) / per};
+}
+inline ChunkSplit chunk_split(int units, long long row_blocks, int cap, int blocks) {
+  return chunk_split_into(units, (int)std::min<long long>(std::min(units, cap), (blocks + row_blocks - 1) / row_blocks));
 }
 
 // ---- device helpers ---------------------------------------------------------------

@@ -256,10 +256,9 @@ static TsnePlan tsne_plan(int n, int chunks) {
   TsnePlan p;
   p.gx = (unsigned)((n + TS_ROWS - 1) / TS_ROWS);
   const int nt = (n + TS_CT - 1) / TS_CT;
-  const int want = chunks > 0 ? std::min(chunks, nt)
-                              : (int)std::min<long long>(std::min(nt, SVAE_TSNE_MAX_CHUNKS), (TS_BLOCKS + (long long)p.gx - 1) / p.gx);
-  p.ch = (nt + want - 1) / want;
-  p.gy = (unsigned)((nt + p.ch - 1) / p.ch);
+  const ChunkSplit s = chunks > 0 ? chunk_split_into(nt, std::min(chunks, nt)) : chunk_split(nt, p.gx, SVAE_TSNE_MAX_CHUNKS, TS_BLOCKS);
+  p.ch = s.per;
+  p.gy = (unsigned)s.parts;
   p.rpad = (long long)p.gx * TS_ROWS;
   return p;
 }

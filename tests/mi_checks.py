@@ -170,6 +170,14 @@ def mi_gate(n):
     return gate
 
 
+def one_class_arguments(x, k):
+    """what mutual_info._mi_check would hand to the device for rows x that all carry one label, a case it refuses (one class is
+    no estimate): the only place the tests spell out that dict"""
+    n = len(x)
+    return dict(x=x, kind="labels", n=n, k=k, kept=np.ones(n, bool), lab=np.zeros(n, np.int32), count=np.array([n]),
+                kk=np.full(n, k, np.int32))
+
+
 def _freeze(*arrays):
     for a in arrays:
         a.setflags(write=False)

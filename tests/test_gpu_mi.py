@@ -89,6 +89,30 @@ def test_ties_and_duplicates(labels):
         check_real(z, y, MC.GRID_K, want, "grid real")
 
 
+def test_constant_y_gives_the_knn_distances():
+    """the walk with the key max(s, s^y) against the walk of the neighbour search: 5 partial row and column tiles, 5 column chunks,
+    so both merges run (decided on the restatements in test_mi_cpu.py)"""
+    from tests import knn_checks as KC
+    from scrubvae_amd.eval import kneighbors, mutual_information
+    x = KC.case(301, 3, 5)[0]
+    _, parts = mutual_information(x, np.zeros((301, 1)), n_neighbors=5, return_parts=True)
+    assert bits(np.sqrt(parts["rho2"])) == bits(kneighbors(x, 5)[0][:, 4])
+
+
+def test_one_class_gives_the_knn_distances():
+    """the walk that admits the row's own label, with every label equal: rows not resident in LDS, 3 column chunks.  One class is
+    no estimate, so mutual_information refuses it: the checked arguments are written out here"""
+    from tests import knn_checks as KC
+    from scrubvae_amd.eval import kneighbors
+    from scrubvae_amd.eval import mutual_info as MI
+    n, d, k = 131, 128, 7
+    x = KC.case(n, d, k)[0]
+    dev = torch.device("cuda", torch.cuda.current_device())
+    run = MI._MiRun(MC.one_class_arguments(x, k), dev)
+    run.run(torch.zeros(2, dtype=torch.float64, device=dev))
+    assert bits(np.sqrt(run.parts()["rho2"])) == bits(kneighbors(x, k)[0][:, k - 1])
+
+
 def test_views_give_the_bits_of_the_contiguous_copy():
     from scrubvae_amd import _lib, ops
     from scrubvae_amd.eval import mutual_information

@@ -206,6 +206,77 @@ def test_new_exports_have_signatures():
     assert NB._KNN_CALLS.keys() >= {"knn"} and NB._KNN_LAST.keys() >= {"work", "chunks"}
 
 
+SPLIT_N = (2, 63, 64, 65, 301, 1037, 4096, 4097, 32775, 40000, 100000, 2 ** 31 - 1)
+
+
+def _ceil(a, b):
+    return -(-a // b)
+
+
+def _split(units, row_blocks, cap, blocks=512):
+    """the rule that splits inner units over a grid dimension, restated: (units per part, parts that are not empty)"""
+    want = min(units, cap, _ceil(blocks, row_blocks))
+    per = _ceil(units, want)
+    return per, _ceil(units, per)
+
+
+def test_split_rule_gives_the_parents_work_sizes():
+    """every *_work size is a function of the one split rule (csrc/svae_internal.h chunk_split); the sizes asserted here are those
+    of the library before the rule was written once, which passes this test unchanged"""
+    from scrubvae_amd import _lib
+    lib = _lib.lib()
+    checked = 0
+    # the walks over 64 x 64 tiles: at most 8 column chunks; lists of k (uint64, int32) per chunk and padded row
+    for name, kmax in (("svae_knn_work", _lib.KNN_MAX_K), ("svae_mi_work", _lib.MI_MAX_K), ("svae_rank_work", _lib.KNN_MAX_K)):
+        for n in SPLIT_N:
+            for k in (1, kmax):
+                nt = _ceil(n, 64)
+                gy = _split(nt, nt, 8)[1]
+                size = n * k * 16 + gy * n * k * 4 if name == "svae_rank_work" else gy * nt * 64 * k * 12
+                assert getattr(lib, name)(n, k) == (size if k <= n - 1 else 0), (name, n, k)
+                checked += 1
+    for m in SPLIT_N:
+        for n in SPLIT_N:
+            for k in (1, _lib.KNN_MAX_K):
+                rt = _ceil(m, 64)
+                gy = _split(_ceil(n, 64), rt, 8)[1]
+                assert lib.svae_knn_cross_work(m, n, k) == (gy * rt * 64 * k * 12 if k <= n else 0), (m, n, k)
+                checked += 1
+    # silhouette: rows x n pairs, 16, 64 or 256 cluster columns per block in grid z; n < 2^26
+    for n in SPLIT_N:
+        for rows in SPLIT_N:
+            for K in (2, _lib.SIL_MAX_CLUSTERS):
+                nc = 16 if K <= 16 else 64 if K <= 64 else 256
+                gx, gz = _ceil(rows, 64), _ceil(K, nc)
+                gy = _split(_ceil(n, 64), gx * gz, 8)[1]
+                ok = 3 <= n < 2 ** 26 and rows <= n
+                assert lib.svae_silhouette_work(rows, n, K) == (gy * gx * 64 * gz * nc if ok else 0), (rows, n, K)
+                checked += 1
+    # t-SNE repulsion: 256 rows per block, column tiles of 64, at most 8 chunks or the caller's count; n <= 2^26
+    for n in SPLIT_N:
+        for chunks in (0, 1, 3, 8):
+            gx, nt = _ceil(n, 256), _ceil(n, 64)
+            gy = _split(nt, gx, 8)[1] if chunks == 0 else _split(nt, 1, chunks, blocks=2 ** 40)[1]
+            assert lib.svae_tsne_repulsion_work(n, chunks) == (gy * 3 * gx * 256 if n <= 2 ** 26 else 0), (n, chunks)
+            checked += 1
+            for m in SPLIT_N:   # the cross form splits from n alone: the most chunks there are unless the caller names a count
+                gyc = _split(nt, 1, chunks or 8, blocks=2 ** 40)[1]
+                ok = m <= 2 ** 26 and n <= 2 ** 26
+                assert lib.svae_tsne_cross_repulsion_work(m, n, chunks) == (gyc * 3 * _ceil(m, 256) * 256 if ok else 0), (m, n, chunks)
+                checked += 1
+    # density: tiles of 128 x 128 cells, the points in chunks of 32 over at most 128 slices; n <= 2^30
+    for n in SPLIT_N + (1,):
+        for gx in (2, _lib.DENSITY_MAX_GRID):
+            for gy in (2, _lib.DENSITY_MAX_GRID):
+                slices = _split(_ceil(n, 32), _ceil(gx, 128) * _ceil(gy, 128), 128)[1]
+                assert lib.svae_density_work(n, gx, gy) == ((slices * gy * gx + 2 * n) * 8 if n <= 2 ** 30 else 0), (n, gx, gy)
+                checked += 1
+    assert checked == 3 * 24 + 288 + 288 + 48 * 13 + 13 * 4
+    # the rule itself, where a slip would show: the cap, the grid bound and the empty last part
+    assert _split(17, 17, 8) == (3, 6) and _split(5, 5, 8) == (1, 5) and _split(625, 625, 8) == (625, 1)
+    assert _split(65, 65, 8) == (9, 8) and _split(9, 1, 8) == (2, 5)
+
+
 def test_constants_equal_the_headers():
     import os
     import re

@@ -80,6 +80,23 @@ def test_ross_drops_single_labels():
     assert again[0] == I and np.array_equal(again[1], rho2) and np.array_equal(again[2], nz) and again[5].all()
 
 
+def test_constant_y_and_one_class_give_the_knn_distance_on_the_restatements():
+    """what test_gpu_mi.py holds the device's walks to each other with: under a constant y the joint key is s^z, and under one class
+    every other row is a candidate, so rho2 is the square of the k-th neighbour distance of tests/knn_checks.py, bit for bit"""
+    from tests import knn_checks as KC
+    x, _, dist, _ = KC.case(301, 3, 5)
+    rho2 = MC.ksg(x, np.zeros((301, 1)), 5)[1]
+    assert np.sqrt(rho2).tobytes() == np.ascontiguousarray(dist[:, 4]).tobytes()
+    x, _, dist, _ = KC.case(131, 128, 7)
+    _, rho2, _, ki, _, kept = MC.ross(x, np.zeros(131, dtype=np.int64), 7)
+    assert kept.all() and (ki == 7).all()
+    assert np.sqrt(rho2).tobytes() == np.ascontiguousarray(dist[:, 6]).tobytes()
+    # the arguments the device test builds for this case are shaped like the checked ones of a case that is accepted
+    from scrubvae_amd.eval import mutual_info as MI
+    ours, theirs = MC.one_class_arguments(x, 7), MI._mi_check(Z6, C6, 2)
+    assert ours.keys() == theirs.keys() and all(np.asarray(ours[key]).dtype == np.asarray(theirs[key]).dtype for key in ours)
+
+
 @pytest.mark.parametrize("n,d,k", MC.SCORES)
 def test_latent_scores_against_sklearn(n, d, k):
     fs = pytest.importorskip("sklearn.feature_selection")
