@@ -627,6 +627,32 @@ int svae_gmm_mstep_f64(const double* A, int lda, int d, int n, int K, int diag, 
 int svae_gmm_precision_f64(const double* L, const int* rank, const double* w, int d, int K, int ldp, double* P, double* cst, int* bad,
                            void* stream);
 
+/* ---------------------------------------------------------------------- k-means clustering (csrc/kmeans.hip) --- */
+/* Lloyd's iteration of sklearn's KMeans(algorithm="lloyd"), fp64, on the centred rows A [n][lda] of svae_cv_center (as for the
+ * mixture above: column d = 1) and centres C [K][ldc] in that centred frame.  d <= SVAE_CV_MAX_DIM, K <= SVAE_KMEANS_MAX_CLUSTERS.
+ * Every sum runs in a fixed order and there are no floating-point atomics: bit-reproducible. */
+#define SVAE_KMEANS_MAX_CLUSTERS 1024
+/* Assignment.  s(r, c) = ((a0 - c0)^2 + (a1 - c1)^2) + ... in feature order (csrc/pair_tiles.h); every row takes the centre with
+ * the smallest key (s by its bit pattern, then the lower centre index).  Outputs (NULL: not written): label [n], dist [n] = that
+ * s, gap [n] = the second-smallest s minus the smallest (+inf when K = 1), D [n][K] = every s, part [svae_kmeans_assign_blocks(n)]
+ * = the sums of dist over blocks of 64 rows, each in a fixed tree order, changed[0] = the rows with label != prev (an integer count;
+ * needs prev [n], which must not be the label buffer).  Nothing of size n x K is written unless D is given. */
+int svae_kmeans_assign_blocks(int n);
+int svae_kmeans_assign_f64(const double* A, int lda, int d, int n, const double* C, int ldc, int K, const int* prev, int* label,
+                           double* dist, double* gap, double* D, double* part, int* changed, void* stream);
+/* Update.  sums [K][d + 1] = sum over the rows r with label[r] == c of A[r][0..d] (column d: the count), as the product M^T [A | 1]
+ * with the 0/1 membership matrix on the fp64 matrix cores: exact products, so each sum is the plain fp64 sum of its cluster's rows
+ * in a fixed order and does not depend on the numbering of the clusters.  Rows are summed in svae_kmeans_chunks(n, d, K) chunks
+ * (a function of the sizes alone: 256-row units, at most 1024 chunks and at most 2^24 doubles of partials), the chunks added in
+ * a fixed order; part holds chunks * K * (d + 1) doubles.  label values outside [0, K) are counted nowhere. */
+int svae_kmeans_chunks(int n, int d, int K);
+int svae_kmeans_update_f64(const double* A, int lda, int d, int n, const int* label, int K, double* part, double* sums, void* stream);
+/* Finish.  C_new[k] = sums[k][0:d] / sums[k][d], or C_old[k] where that count is 0 (C_new must not be C_old);
+ * rec [3] = {changed[0] (-1 when changed is NULL), sum |C_new - C_old|^2 in a fixed order, the clusters with count 0}: the one
+ * record a host reads per iteration.  (The inertia is svae_gmm_sum_f64 of the assignment's part with div = 1.) */
+int svae_kmeans_finish_f64(const double* sums, int d, int K, const double* C_old, double* C_new, int ldc, const int* changed,
+                           double* rec, void* stream);
+
 /* ---------------------------------------------------------------------- HDBSCAN clustering (csrc/hdbscan.hip) --- */
 /* sklearn HDBSCAN(metric="euclidean") of the reference's eval/cluster.py::dbscan, fp64.  Rows X [n][ld] (the latents converted to
  * fp64, not centred).  Squared distance s = ((x0 - y0)^2 + (x1 - y1)^2) + ... in feature order, no FMA; distance = sqrt(s),

@@ -189,6 +189,11 @@ SIGNATURES = {
     "svae_gmm_chunks": (I, [I, I]),
     "svae_gmm_mstep_f64": (I, [P, I, I, I, I, I, P, D, P, P, P, P, P, P, P, P, P, P]),
     "svae_gmm_precision_f64": (I, [P, P, P, I, I, I, P, P, P, P]),
+    "svae_kmeans_assign_blocks": (I, [I]),
+    "svae_kmeans_assign_f64": (I, [P, I, I, I, P, I, I, P, P, P, P, P, P, P, P]),
+    "svae_kmeans_chunks": (I, [I, I, I]),
+    "svae_kmeans_update_f64": (I, [P, I, I, I, P, I, P, P, P]),
+    "svae_kmeans_finish_f64": (I, [P, I, I, P, P, I, P, P, P]),
     "svae_hdb_core": (I, [P, I, I, I, I, P, P]),
     "svae_hdb_boruvka": (I, [P, I, I, I, P, P, P, D, I, P, P, P, P, P]),
     "svae_hdb_relabel": (I, [P, I, P, P]),
@@ -262,6 +267,7 @@ def last_error():
 
 CV_MAX_DIM, CV_MAX_TARGETS, CV_MAX_CLASSES, CV_MAX_FOLDS, CV_MAX_GROUPS = 128, 8, 64, 10, 640  # include/scrubvae_hip.h SVAE_CV_*
 GMM_MAX_COMPONENTS, GMM_MAX_TRIALS = 64, 8  # include/scrubvae_hip.h SVAE_GMM_*
+KMEANS_MAX_CLUSTERS = 1024  # include/scrubvae_hip.h SVAE_KMEANS_MAX_CLUSTERS
 MMD_WORK_WORDS = 8256  # include/scrubvae_hip.h SVAE_MMD_WORK_WORDS
 MMD_NULL_MAX = 65536  # include/scrubvae_hip.h SVAE_MMD_NULL_MAX
 SIL_MAX_CLUSTERS = 4096  # include/scrubvae_hip.h SVAE_SIL_MAX_CLUSTERS

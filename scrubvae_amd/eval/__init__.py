@@ -1,4 +1,4 @@
-from .cluster import GaussianMixture, dbscan, gmm  # noqa: F401
+from .cluster import GaussianMixture, KMeans, dbscan, gmm, kmeans  # noqa: F401
 from .density import DensityGrid, DensityMap, density_map, density_regions  # noqa: F401
 from .embed import TSNE, tsne, tsne_affinities  # noqa: F401
 from .embed_transform import TSNEMap, tsne_transform  # noqa: F401

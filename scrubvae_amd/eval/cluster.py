@@ -23,6 +23,28 @@ Differences from sklearn, by design:
   - k-means++ distances are sum (x - c)^2, not |x|^2 - 2 x.c + |c|^2.
   - the initial covariance is exactly reg_covar * I (sklearn's carries a rounding residue of order |x|^2 eps).
 Only covariance_type in {"full", "diag"}, init_params="k-means++" and n_init=1 are supported; d <= 128 and n_components <= 64.
+
+    KMeans(n_clusters=8, *, init="k-means++", n_init="auto", max_iter=300, tol=1e-4, verbose=0, random_state=None, copy_x=True,
+           algorithm="lloyd")
+    kmeans(latents, label="cluster", path=None, n_clusters=25, random_state=None) -> (k_pred, model)
+
+KMeans restates sklearn 1.7's KMeans(algorithm="lloyd") with unit sample weights: rows centred by their mean, tol scaled by the mean
+column variance, the same host draws (k-means++ through the seeding above, or RandomState.choice for init="random", nothing else
+between restarts), Lloyd's iteration with sklearn's two stopping tests, the relocation of empty clusters, the extra assignment
+after a stop by tol, the restart kept by inertia unless it is the same clustering renumbered.  The iteration runs in
+csrc/kmeans.hip (assignment, per-cluster sums on the fp64 matrix cores, new centres); the host reads one record of three numbers
+per iteration.  Input rows are read as for the mixture: fp32 once, fp64 after that.
+
+Differences from sklearn's KMeans, by design:
+  - all arithmetic is fp64 in a fixed order, also for float32 input; distances are sum (x - c)^2 in feature order, not
+    |x|^2 - 2 x.c + |c|^2, and a row at equal distance from two centres takes the lower index.
+  - new centres are sums / count (sklearn multiplies by 1 / count); the shift is sum |new - old|^2 (sklearn squares the rounded
+    norms); a cluster emptied by a relocation keeps its old centre; tol's variance is the centred rows' sum of squares / (n d).
+  - empty clusters take the rows farthest from their centres with the lower row first on equal distances (sklearn's argpartition
+    leaves ties open).
+  - predict, transform and score centre the new rows at their own mean and shift the centres alike, as the mixture's predict does.
+Only unit sample weights, algorithm="lloyd" and init in {"k-means++", "random", an array} are supported; d <= 128,
+n_clusters <= 1024 and n_samples >= n_clusters.
 """
 from __future__ import annotations
 
@@ -50,7 +72,8 @@ _NOT_PD = ("Fitting the mixture model failed because some components have ill-de
 
 
 class ConvergenceWarning(_MetricsConvergenceWarning):
-    """An EM fit stopped at max_iter with the lower bound still moving by tol or more (sklearn's ConvergenceWarning)."""
+    """An EM fit stopped at max_iter with the lower bound still moving by tol or more, or a k-means fit ended with fewer than
+    n_clusters distinct labels (sklearn's ConvergenceWarning)."""
 
 
 def check_random_state(seed):
@@ -96,15 +119,14 @@ def _host_log_det(P, diag):
     return np.log(P).sum(1) if diag else np.log(np.diagonal(P, axis1=1, axis2=2)).sum(1)
 
 
-class _Rows:
+class _Centred:
     """fp32 rows [n, d] on the device, centred once into the fp64 matrix A [n][lda] (svae_cv_center) every kernel reads, and the
-    device parameters of the E-step (means in the centred frame, precision factors, constants)."""
+    k-means++ seeding of K of them."""
 
-    def __init__(self, x, K, diag, device):
+    def __init__(self, x, K, device):
         n, d = x.shape
-        self.n, self.d, self.K, self.diag, self.device = n, d, K, bool(diag), device
+        self.n, self.d, self.K, self.device = n, d, K, device
         self.lda = ops.pad16(d + 1)
-        self.ldp = d if diag else _pad8(d)
         f64 = dict(dtype=torch.float64, device=device)
         self.f64 = f64
         x = x.to(device=device, dtype=torch.float32).contiguous()
@@ -114,6 +136,47 @@ class _Rows:
         check(_lib.lib().svae_cv_center(x.data_ptr(), d, d, None, 0, 0, perm.data_ptr(), n, self.mean_d.data_ptr(), self.A.data_ptr(),
                                         self.lda, ops._stream()), "cv_center")
         self.mean = self.mean_d.cpu().numpy()
+
+    def kmeans_pp(self, rs):
+        """sklearn's _kmeans_plusplus with unit sample weights: host draws, device distances; returns the K seed row indices"""
+        n, K = self.n, self.K
+        L = _lib.lib()
+        st = ops._stream()
+        T = 2 + int(np.log(K))
+        nb = L.svae_gmm_kpp_blocks(n)
+        f64 = self.f64
+        closest, tot = torch.empty(n, **f64), torch.empty(nb, **f64)
+        d2, part = torch.empty(T, n, **f64), torch.empty(T, nb, **f64)
+        vals = torch.empty(T, **f64)
+        cand = torch.empty(T, dtype=torch.int32, device=self.device)
+        out = torch.empty(2, **f64)  # pot, then the chosen row as an int32 pair view
+        out_i = torch.empty(2, dtype=torch.int32, device=self.device)
+        center_id = int(rs.choice(n, p=np.ones(n) / n))
+        cand[0] = center_id
+        indices = [center_id]
+        check(L.svae_gmm_kpp_round(self.A.data_ptr(), self.lda, self.d, n, None, 1, cand.data_ptr(), closest.data_ptr(), tot.data_ptr(),
+                                   d2.data_ptr(), part.data_ptr(), out.data_ptr(), out_i.data_ptr(), out_i[1:].data_ptr(), st),
+              "gmm_kpp_round")
+        pot = float(out[0].item())
+        for _ in range(1, K):
+            rv = rs.uniform(size=T) * pot
+            vals.copy_(torch.from_numpy(rv))
+            check(L.svae_gmm_kpp_round(self.A.data_ptr(), self.lda, self.d, n, vals.data_ptr(), T, cand.data_ptr(), closest.data_ptr(),
+                                       tot.data_ptr(), d2.data_ptr(), part.data_ptr(), out.data_ptr(), out_i.data_ptr(),
+                                       out_i[1:].data_ptr(), st), "gmm_kpp_round")
+            pot = float(out[0].item())
+            indices.append(int(out_i[0].item()))
+        return np.array(indices, dtype=np.int64)
+
+
+class _Rows(_Centred):
+    """The centred rows and the device parameters of the E-step (means in the centred frame, precision factors, constants)."""
+
+    def __init__(self, x, K, diag, device):
+        super().__init__(x, K, device)
+        d, f64 = self.d, self.f64
+        self.diag = bool(diag)
+        self.ldp = d if diag else _pad8(d)
         self.mu = torch.empty(K, d, **f64)
         self.P = torch.zeros(K, d, self.ldp, **f64) if not diag else torch.empty(K, d, **f64)
         self.cst = torch.empty(K, **f64)
@@ -148,37 +211,6 @@ class _Rows:
         lpn = torch.empty(self.n, **self.f64)
         self.estep(resp=resp, lpn=lpn)
         return resp, lpn
-
-    def kmeans_pp(self, rs):
-        """sklearn's _kmeans_plusplus with unit sample weights: host draws, device distances; returns the K seed row indices"""
-        n, K = self.n, self.K
-        L = _lib.lib()
-        st = ops._stream()
-        T = 2 + int(np.log(K))
-        nb = L.svae_gmm_kpp_blocks(n)
-        f64 = self.f64
-        closest, tot = torch.empty(n, **f64), torch.empty(nb, **f64)
-        d2, part = torch.empty(T, n, **f64), torch.empty(T, nb, **f64)
-        vals = torch.empty(T, **f64)
-        cand = torch.empty(T, dtype=torch.int32, device=self.device)
-        out = torch.empty(2, **f64)  # pot, then the chosen row as an int32 pair view
-        out_i = torch.empty(2, dtype=torch.int32, device=self.device)
-        center_id = int(rs.choice(n, p=np.ones(n) / n))
-        cand[0] = center_id
-        indices = [center_id]
-        check(L.svae_gmm_kpp_round(self.A.data_ptr(), self.lda, self.d, n, None, 1, cand.data_ptr(), closest.data_ptr(), tot.data_ptr(),
-                                   d2.data_ptr(), part.data_ptr(), out.data_ptr(), out_i.data_ptr(), out_i[1:].data_ptr(), st),
-              "gmm_kpp_round")
-        pot = float(out[0].item())
-        for _ in range(1, K):
-            rv = rs.uniform(size=T) * pot
-            vals.copy_(torch.from_numpy(rv))
-            check(L.svae_gmm_kpp_round(self.A.data_ptr(), self.lda, self.d, n, vals.data_ptr(), T, cand.data_ptr(), closest.data_ptr(),
-                                       tot.data_ptr(), d2.data_ptr(), part.data_ptr(), out.data_ptr(), out_i.data_ptr(),
-                                       out_i[1:].data_ptr(), st), "gmm_kpp_round")
-            pot = float(out[0].item())
-            indices.append(int(out_i[0].item()))
-        return np.array(indices, dtype=np.int64)
 
 
 class _EM:
@@ -411,9 +443,14 @@ class _Fitted(GaussianMixture):
 
 
 def _as_device_model(model):
-    """model itself when it is a GaussianMixture of this module, else a copy of sklearn's fitted attribute names of it"""
-    if isinstance(model, GaussianMixture):
+    """model itself when it is a GaussianMixture or KMeans of this module, else a copy of sklearn's fitted attribute names of it"""
+    if isinstance(model, (GaussianMixture, KMeans)):
         return model
+    if hasattr(model, "cluster_centers_"):
+        m = KMeans(n_clusters=len(model.cluster_centers_))
+        m.cluster_centers_ = np.asarray(model.cluster_centers_, np.float64)
+        m.n_features_in_ = m.cluster_centers_.shape[1]
+        return m
     m = _Fitted(n_components=len(model.weights_), covariance_type=model.covariance_type)
     m.weights_ = np.asarray(model.weights_, np.float64)
     m.means_ = np.asarray(model.means_, np.float64)
@@ -477,3 +514,284 @@ def dbscan(latents, eps=0.1, min_samples=500, label="cluster", path="./results/"
     print(len(np.unique(k_pred)))
     np.save(preds_path, k_pred)
     return k_pred
+
+
+# ---- k-means ------------------------------------------------------------------------------------------------------------------------
+KMEANS_INITS = ("k-means++", "random")
+_km_device_of = functools.partial(_device._device_of, who="KMeans runs on the GPU (csrc/kmeans.hip); no device is available")
+
+
+def _relocation_rows(dist, n_empty):
+    """the rows the empty clusters take: by descending distance to their own centre, the lower row first on a tie"""
+    return np.lexsort((np.arange(len(dist)), -dist))[:n_empty]
+
+
+def _is_same_clustering(labels1, labels2, n_clusters):
+    """sklearn's _is_same_clustering: labels2 is labels1 with the clusters renumbered"""
+    mapping = np.full(n_clusters, -1, dtype=np.int64)
+    u, first = np.unique(labels1, return_index=True)
+    mapping[u] = labels2[first]
+    return bool((mapping[labels1] == labels2).all())
+
+
+class _Lloyd:
+    """Device state of Lloyd's iteration on the centred rows R (_Centred): two centre and two label buffers that swap roles, the
+    distances, the partial buffers of csrc/kmeans.hip and the record of one iteration."""
+
+    def __init__(self, R, fitting=True):
+        self.R = R
+        n, d, K, dev, f64 = R.n, R.d, R.K, R.device, R.f64
+        L = _lib.lib()
+        self.nb = L.svae_kmeans_assign_blocks(n)
+        self.ipart = torch.empty(self.nb, **f64)
+        self.total = torch.empty(1, **f64)
+        if not fitting:  # assignment only
+            self.label = [torch.empty(n, dtype=torch.int32, device=dev)]
+            return
+        self.chunks = L.svae_kmeans_chunks(n, d, K)
+        self.C = [torch.empty(K, d, **f64), torch.empty(K, d, **f64)]
+        self.label = [torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev)]
+        self.dist = torch.empty(n, **f64)
+        self.part = torch.empty(self.chunks * K * (d + 1), **f64)
+        self.sums = torch.empty(K, d + 1, **f64)
+        self.changed = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.rec = torch.empty(3, **f64)
+
+    def assign(self, C, label=None, prev=None, dist=None, gap=None, D=None, part=None, changed=None):
+        R = self.R
+        check(_lib.lib().svae_kmeans_assign_f64(R.A.data_ptr(), R.lda, R.d, R.n, C.data_ptr(), C.stride(0), C.shape[0], ops._p(prev),
+                                                ops._p(label), ops._p(dist), ops._p(gap), ops._p(D), ops._p(part), ops._p(changed),
+                                                ops._stream()), "kmeans_assign_f64")
+
+    def update(self, label):
+        R = self.R
+        check(_lib.lib().svae_kmeans_update_f64(R.A.data_ptr(), R.lda, R.d, R.n, label.data_ptr(), R.K, self.part.data_ptr(),
+                                                self.sums.data_ptr(), ops._stream()), "kmeans_update_f64")
+
+    def finish(self, C_old, C_new, changed=None):
+        """-> host (rows whose label changed, shift, empty clusters)"""
+        R = self.R
+        check(_lib.lib().svae_kmeans_finish_f64(self.sums.data_ptr(), R.d, R.K, C_old.data_ptr(), C_new.data_ptr(), C_old.stride(0),
+                                                ops._p(changed), self.rec.data_ptr(), ops._stream()), "kmeans_finish_f64")
+        rec = self.rec.cpu().numpy()
+        return int(rec[0]), float(rec[1]), int(rec[2])
+
+    def inertia(self):
+        """the sum of the last assignment's distances (its block sums, added in a fixed order)"""
+        check(_lib.lib().svae_gmm_sum_f64(self.ipart.data_ptr(), self.nb, 1.0, self.total.data_ptr(), ops._stream()), "gmm_sum_f64")
+        return float(self.total.item())
+
+    def sum_of_squares(self):
+        """sum |a|^2 over the centred rows: the distances to one zero centre"""
+        zero = torch.zeros(1, self.R.d, **self.R.f64)
+        self.assign(zero, part=self.ipart)
+        return self.inertia()
+
+    def relocate(self, label):
+        """the rare path: every empty cluster, in ascending order, takes one far row out of its cluster's sum and count"""
+        d = self.R.d
+        empty = np.flatnonzero(self.sums[:, d].cpu().numpy() == 0)
+        lab = label.cpu().numpy()
+        for c, r in zip(empty, _relocation_rows(self.dist.cpu().numpy(), len(empty))):
+            row = self.R.A[int(r), :d + 1]
+            self.sums[int(lab[r])] -= row
+            self.sums[int(c)] = row
+
+    def step(self, C, C_new, label, prev):
+        """one iteration from the centres C: label, dist, C_new -> (changed, shift, empty clusters before relocation)"""
+        self.assign(C, label=label, prev=prev, dist=self.dist, part=self.ipart, changed=self.changed)
+        self.update(label)
+        changed, shift, n_empty = self.finish(C, C_new, self.changed)
+        if n_empty:
+            self.relocate(label)
+            _, shift, _ = self.finish(C, C_new, self.changed)
+        return changed, shift, n_empty
+
+    def run(self, C0, max_iter, tol_, verbose=0):
+        """sklearn's _kmeans_single_lloyd from the centres C0 (device [K, d], centred frame) -> (labels, inertia, centres, n_iter),
+        labels and centres on the device"""
+        C, C_new = self.C
+        C.copy_(C0)
+        label, prev = self.label
+        prev.fill_(-1)
+        strict, n_iter = False, 0
+        for n_iter in range(1, max_iter + 1):
+            changed, shift, _ = self.step(C, C_new, label, prev)
+            C, C_new = C_new, C
+            if verbose:
+                print(f"Iteration {n_iter - 1}, inertia {self.inertia()}.")
+            if changed == 0:
+                strict = True
+                if verbose:
+                    print(f"Converged at iteration {n_iter - 1}: strict convergence.")
+                break
+            if shift <= tol_:
+                if verbose:
+                    print(f"Converged at iteration {n_iter - 1}: center shift {shift} within tolerance {tol_}.")
+                break
+            label, prev = prev, label
+        if not strict:
+            self.assign(C, label=label, dist=self.dist, part=self.ipart)
+        return label, self.inertia(), C, n_iter
+
+
+class KMeans:
+    """sklearn.cluster.KMeans (algorithm="lloyd", unit sample weights) fitted on the GPU.
+
+    X may be a numpy array or a torch tensor, on the CPU or the device, of shape [n, d]; rows are read as fp32 (fp64 input is
+    rounded to fp32 once) and all arithmetic after that is fp64 (module docstring: differences from sklearn).  Fitted attributes
+    are host numpy arrays with sklearn's names and shapes, so a fitted object pickles and unpickles without a GPU."""
+
+    def __init__(self, n_clusters=8, *, init="k-means++", n_init="auto", max_iter=300, tol=1e-4, verbose=0, random_state=None,
+                 copy_x=True, algorithm="lloyd"):
+        self.n_clusters = n_clusters
+        self.init = init
+        self.n_init = n_init
+        self.max_iter = max_iter
+        self.tol = tol
+        self.verbose = verbose
+        self.random_state = random_state
+        self.copy_x = copy_x
+        self.algorithm = algorithm
+
+    def _init_array(self):
+        return None if isinstance(self.init, str) or callable(self.init) else self.init
+
+    def _check_parameters(self):
+        if self.algorithm != "lloyd":
+            raise ValueError(f"algorithm {self.algorithm!r} is not supported: only 'lloyd'")
+        if callable(self.init):
+            raise ValueError("a callable init is not supported: use 'k-means++', 'random' or an array")
+        if isinstance(self.init, str) and self.init not in KMEANS_INITS:
+            raise ValueError(f"init {self.init!r} is not supported: use one of {KMEANS_INITS} or an array")
+        if not isinstance(self.n_clusters, numbers.Integral) or self.n_clusters < 1:
+            raise ValueError(f"n_clusters must be an integer >= 1, got {self.n_clusters!r}")
+        if self.n_clusters > _lib.KMEANS_MAX_CLUSTERS:
+            raise ValueError(f"n_clusters={self.n_clusters} > {_lib.KMEANS_MAX_CLUSTERS} is not supported")
+        if self.n_init != "auto" and (not isinstance(self.n_init, numbers.Integral) or self.n_init < 1):
+            raise ValueError(f"n_init must be 'auto' or an integer >= 1, got {self.n_init!r}")
+        if not isinstance(self.max_iter, numbers.Integral) or self.max_iter < 1:
+            raise ValueError(f"max_iter must be an integer >= 1, got {self.max_iter!r}")
+        if not self.tol >= 0:
+            raise ValueError(f"tol must be >= 0, got {self.tol!r}")
+
+    def _rows(self, X, fitting):
+        """validated fp32 rows (host or device) -- every ValueError comes before the device is touched"""
+        if fitting:
+            self._check_parameters()
+        if hasattr(X, "tocsr") or (torch.is_tensor(X) and X.layout != torch.strided):
+            raise ValueError("sparse input is not supported")
+        x = _rows32(X)
+        n, d = x.shape
+        if d > _lib.CV_MAX_DIM:
+            raise ValueError(f"{d} features > {_lib.CV_MAX_DIM} is not supported")
+        if d < 1 or n < 1:
+            raise ValueError(f"Found array with shape {tuple(x.shape)}")
+        if fitting:
+            if n < self.n_clusters:
+                raise ValueError(f"n_samples={n} should be >= n_clusters={self.n_clusters}.")
+        elif d != self.n_features_in_:
+            raise ValueError(f"X has {d} features, but KMeans is expecting {self.n_features_in_} features as input.")
+        return x
+
+    def _init_centres(self, d):
+        """the init array as fp64 [K, d] (None for a named init), refused when its shape is wrong or a value is not finite"""
+        init = self._init_array()
+        if init is None:
+            return None
+        c = init.detach().cpu().numpy() if torch.is_tensor(init) else np.asarray(init)
+        c = np.array(c, dtype=np.float64)
+        if c.shape != (self.n_clusters, d):
+            raise ValueError(f"The shape of the initial centers {c.shape} does not match (n_clusters, n_features) = "
+                             f"({self.n_clusters}, {d}).")
+        if not np.isfinite(c).all():
+            raise ValueError("The initial centers contain NaN or infinity.")
+        return c
+
+    def _fit(self, X, sample_weight=None):
+        if sample_weight is not None:
+            raise ValueError("sample_weight is not supported: only unit weights")
+        x = self._rows(X, True)
+        K = int(self.n_clusters)
+        init = self._init_centres(x.shape[1])
+        n_init = self.n_init
+        if n_init == "auto":
+            n_init = 1 if init is not None or self.init == "k-means++" else 10
+        if init is not None and n_init != 1:
+            warnings.warn("Explicit initial center position passed: performing only one init in KMeans instead of "
+                          f"n_init={n_init}.", RuntimeWarning)
+            n_init = 1
+        dev = _km_device_of(x)
+        with torch.cuda.device(dev):
+            xt = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
+            rs = check_random_state(self.random_state)
+            R = _Centred(xt, K, dev)
+            n, d = R.n, R.d
+            it = _Lloyd(R)
+            tol_ = float(self.tol) * it.sum_of_squares() / (n * d)
+            best = None
+            for _ in range(n_init):
+                if init is not None:
+                    C0 = torch.from_numpy(init - R.mean[None, :]).to(dev)
+                else:
+                    seeds = R.kmeans_pp(rs) if self.init == "k-means++" else rs.choice(n, size=K, replace=False, p=np.ones(n) / n)
+                    C0 = R.A[torch.as_tensor(np.asarray(seeds, np.int64), device=dev), :d]
+                label, inertia, C, n_iter = it.run(C0, int(self.max_iter), tol_, self.verbose)
+                labels = label.cpu().numpy()
+                if best is None or (inertia < best[1] and not _is_same_clustering(labels, best[0], K)):
+                    best = (labels, inertia, C.cpu().numpy(), n_iter)
+            labels, inertia, centres, n_iter = best
+            if len(np.unique(labels)) < K:
+                warnings.warn(f"Number of distinct clusters ({len(np.unique(labels))}) found smaller than n_clusters ({K}). Possibly "
+                              "due to duplicate points in X.", ConvergenceWarning)
+            self.cluster_centers_ = centres + R.mean[None, :]
+            self.labels_ = labels.astype(np.int32)
+            self.inertia_ = float(inertia)
+            self.n_iter_ = int(n_iter)
+            self.n_features_in_ = d
+            self._tol = tol_
+        return self
+
+    def fit(self, X, y=None, sample_weight=None):
+        return self._fit(X, sample_weight)
+
+    def fit_predict(self, X, y=None, sample_weight=None):
+        return self._fit(X, sample_weight).labels_
+
+    def fit_transform(self, X, y=None, sample_weight=None):
+        return self._fit(X, sample_weight).transform(X)
+
+    def _assigned(self, X, want_D=False):
+        """the assignment of new rows to the fitted centres -> (labels, D [n, K] of squared distances or None, inertia)"""
+        if not hasattr(self, "cluster_centers_"):
+            raise RuntimeError("This KMeans instance is not fitted yet. Call 'fit' first.")
+        x = self._rows(X, False)
+        dev = _km_device_of(x)
+        centres = np.asarray(self.cluster_centers_, np.float64)
+        with torch.cuda.device(dev):
+            xt = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
+            R = _Centred(xt, centres.shape[0], dev)
+            it = _Lloyd(R, fitting=False)
+            C = torch.from_numpy(np.ascontiguousarray(centres - R.mean[None, :])).to(dev)
+            D = torch.empty(R.n, R.K, **R.f64) if want_D else None
+            it.assign(C, label=it.label[0], D=D, part=it.ipart)
+            return it.label[0].cpu().numpy(), (D.cpu().numpy() if want_D else None), it.inertia()
+
+    def predict(self, X):
+        return self._assigned(X)[0]
+
+    def transform(self, X):
+        """distances [n, K] to the centres: the correctly rounded sqrt of the squared distances"""
+        return np.sqrt(self._assigned(X, want_D=True)[1])
+
+    def score(self, X, y=None, sample_weight=None):
+        if sample_weight is not None:
+            raise ValueError("sample_weight is not supported: only unit weights")
+        return -self._assigned(X)[2]
+
+
+@_check_model_exists
+def kmeans(latents, n_clusters=25, random_state=None):
+    """KMeans(n_clusters, random_state=random_state) fitted to the latents -> (k_pred, model), cached as gmm() caches:
+    {path}{label}_kmeans.p and .npy"""
+    return KMeans(n_clusters=n_clusters, random_state=random_state).fit(latents)
