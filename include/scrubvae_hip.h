@@ -890,6 +890,35 @@ int svae_mi_radius(const double* Z, int ld, int d, int n, const double* Y, int q
 int svae_mi_counts(const double* Z, int ld, int d, int n, const double* Y, int q, const double* rho2, int* nz, int* ny, void* stream);
 int svae_mi_psi_sums(const int* a, const int* b, long long n, double* out, void* stream);
 
+/* ------------------------------------------------------- Conditional mutual information by kNN; local permutations (csrc/mi.hip) */
+/* The integer parts of the kNN estimate of I(z; y | c) (Frenzel and Pompe 2007) and the draw of its local permutation null (Runge
+ * 2018).  Z, Y, n, k and the squared distances s^z, s^y are those of svae_mi_radius (Y is always given here).  The condition is
+ * either C [n][p] fp64 rows, contiguous, 1 <= p <= SVAE_CMI_MAX_C, with s^c_ij summed like s^y_ij, or clab [n] int32; exactly one
+ * of the two is non-null.  The row itself is left out by index.
+ *
+ * svae_cmi_radius: rho2 [n].  With C: the k-th smallest max(s^z_ij, s^y_ij, s^c_ij) over j != i.  With clab: the k-th smallest
+ * max(s^z_ij, s^y_ij) over the j != i with clab[j] == clab[i]; the caller guarantees that every class has more than k rows (with
+ * fewer, rho2[i] is left unwritten).  The walk, buffer, finish kernel and svae_mi_work(n, k) workspace of svae_mi_radius.
+ * svae_cmi_counts: int32 [n], strict, over j != i.  With C: nzc = #{max(s^z_ij, s^c_ij) < rho2[i]}, nyc = #{max(s^y_ij, s^c_ij) <
+ * rho2[i]}, nc = #{s^c_ij < rho2[i]}.  With clab: nzc = #{clab[j] == clab[i], s^z_ij < rho2[i]}, nyc likewise with s^y, and nc
+ * must be null (the class size is the host's).  Integer adds only: exact, independent of scheduling and of the column chunks.
+ * The psi sums are svae_mi_psi_sums, called twice for the three arrays.
+ *
+ * svae_local_permutations: out [P][n] int32.  nbr [n][kp] int32 holds the donors of every row, order [P][n] int32 a visiting
+ * order per permutation, scan [P][n][kp] uint8 per row a permutation of 0..kp-1.  For permutation p every row starts unused; the
+ * rows are visited as i = order[p][t], t = 0..n-1; the donors j = nbr[i][scan[p][i][e]] are tried for e = 0, 1, ... up to the
+ * first unused one, and when all kp are used the last one tried is kept (so a donor can serve twice); then out[p][i] = j and j
+ * is used.  1 <= kp <= SVAE_CMI_MAX_DONORS, 1 <= n <= 2^19 (the used-bitmap of a permutation sits in 64 KiB of LDS), 1 <= P <=
+ * SVAE_MMD_NULL_MAX.  The caller guarantees the ranges of the entries; an entry out of range reads and marks nothing.  One wave per
+ * permutation, one wave-step per visit; the result is a function of the inputs alone. */
+#define SVAE_CMI_MAX_C 4
+#define SVAE_CMI_MAX_DONORS 64
+int svae_cmi_radius(const double* Z, int ld, int d, int n, const double* Y, int q, const double* C, int p, const int* clab, int k,
+                    void* work, double* rho2, void* stream);
+int svae_cmi_counts(const double* Z, int ld, int d, int n, const double* Y, int q, const double* C, int p, const int* clab,
+                    const double* rho2, int* nzc, int* nyc, int* nc, void* stream);
+int svae_local_permutations(const int* nbr, int n, int kp, const int* order, const unsigned char* scan, int P, int* out, void* stream);
+
 /* ------------------------------------------------------- Ranks of given neighbours; embedding-quality sums (csrc/rank.hip) ---- */
 /* svae_knn_ranks: X [n][ld] fp64 rows, not centred, d >= 1, 2 <= n < 2^31; idx [n][k] int32, 1 <= k <= min(n - 1, SVAE_KNN_MAX_K),
  * row i holding k distinct indices in [0, n), none equal to i.  rank [n][k] int32:

@@ -229,6 +229,9 @@ SIGNATURES = {
     "svae_mi_radius": (I, [P, I, I, I, P, I, P, P, I, P, P, P]),
     "svae_mi_counts": (I, [P, I, I, I, P, I, P, P, P, P]),
     "svae_mi_psi_sums": (I, [P, P, LL, P, P]),
+    "svae_cmi_radius": (I, [P, I, I, I, P, I, P, I, P, I, P, P, P]),
+    "svae_cmi_counts": (I, [P, I, I, I, P, I, P, I, P, P, P, P, P, P]),
+    "svae_local_permutations": (I, [P, I, I, P, P, I, P, P]),
     "svae_rank_work": (LL, [I, I]),
     "svae_knn_ranks": (I, [P, I, I, I, P, I, P, P, P]),
     "svae_rank_curves": (I, [P, I, I, I, P, P, P, P]),
@@ -273,6 +276,7 @@ MMD_NULL_MAX = 65536  # include/scrubvae_hip.h SVAE_MMD_NULL_MAX
 SIL_MAX_CLUSTERS = 4096  # include/scrubvae_hip.h SVAE_SIL_MAX_CLUSTERS
 KNN_MAX_K = 90  # include/scrubvae_hip.h SVAE_KNN_MAX_K
 MI_MAX_K, MI_MAX_Y = 32, 4  # include/scrubvae_hip.h SVAE_MI_*
+CMI_MAX_C, CMI_MAX_DONORS = 4, 64  # include/scrubvae_hip.h SVAE_CMI_*
 TSNE_SEARCH_STEPS, TSNE_MAX_CHUNKS = 100, 8  # include/scrubvae_hip.h SVAE_TSNE_*
 DENSITY_MAX_GRID = 1024  # include/scrubvae_hip.h SVAE_DENSITY_MAX_GRID
 HSIC_MAX_Y, HSIC_PERMS = 4, 16  # include/scrubvae_hip.h SVAE_HSIC_*

@@ -14,6 +14,9 @@
 // LDS array; s^y is summed in feature order like s^z.  A finish kernel merges the column chunks by rank and writes only the value
 // of the k-th key.  The counts are int32, combined over the four waves in LDS and over the column chunks by global integer
 // atomics: exact, and independent of scheduling and of the chunking.
+//
+// Below them, on the same walk, buffer, finish kernel and psi sums: the integer parts of the conditional estimate I(z; y | c)
+// (cmi_radius_kernel, cmi_count_kernel) and the draw of its local permutation null (cmi_local_perm_kernel).
 #include "svae_internal.h"
 
 #include "fixed_sum.h"
@@ -210,6 +213,196 @@ __global__ __launch_bounds__(256) void mi_psi_sums_kernel(const int* __restrict_
   if (threadIdx.x == 0) out[blockIdx.x] = red[0];
 }
 
+// ---- conditional mutual information I(z; y | c): Frenzel-Pompe (2007) for a real c, the estimate inside every class for labels ----
+//   cmi_radius_kernel   rho2 [n]: the k-th smallest key of every row over j != i.  Real c: the key is max(s^z_ij, s^y_ij, s^c_ij).
+//                       Labels: the key is max(s^z_ij, s^y_ij) over the j with clab_j == clab_i.  The walk and buffer of
+//                       mi_radius_kernel with one k for every row; mi_finish_kernel merges the chunks.
+//   cmi_count_kernel    real c: nzc = #{max(s^z, s^c) < rho2_i}, nyc = #{max(s^y, s^c) < rho2_i}, nc = #{s^c < rho2_i};
+//                       labels: nzc = #{same label, s^z < rho2_i}, nyc = #{same label, s^y < rho2_i}; all strict, over j != i
+// c is staged and summed like y (mi_stage_y, mi_sy): the two caps are one number.
+static_assert(SVAE_CMI_MAX_C == SVAE_MI_MAX_Y, "c is staged by mi_stage_y and summed by mi_sy");
+
+// dynamic LDS of the two kernels, in doubles, after the rows and candidates of pair_tiles.h
+constexpr int CMI_Y = PAIR_LDS_KT;                        // cy [64][4] fp64: y of the tile's columns
+constexpr int CMI_C = CMI_Y + HT * SVAE_MI_MAX_Y;         // cc [64][4] fp64: c of the tile's columns
+constexpr int CMI_LAB = CMI_C + HT * SVAE_CMI_MAX_C;      // clab [64] int32: label of the tile's columns
+constexpr int CMI_KEY = CMI_LAB + HT / 2;                 // the buffers of knn_buffer.h (radius kernel)
+constexpr int CMI_END = CMI_KEY + MiBuf::WORDS;
+constexpr size_t CMI_RADIUS_LDS = (size_t)CMI_END * sizeof(double);  // 145,152 B: one block per CU
+static_assert(CMI_RADIUS_LDS == MI_RADIUS_LDS + 2048 && CMI_RADIUS_LDS <= 160 * 1024, "LDS per workgroup");
+constexpr int CMI_CNT = CMI_KEY;                          // zc, yc, c counts [3][4][64] int32 (count kernel)
+constexpr size_t CMI_COUNT_LDS = (size_t)(CMI_CNT + 3 * 4 * HR / 2) * sizeof(double);  // 48,896 B
+static_assert(CMI_COUNT_LDS <= 64 * 1024, "below the default dynamic LDS limit");
+
+__device__ __forceinline__ u64 cmi_bits(double s) { return (u64)__double_as_longlong(s); }
+__device__ __forceinline__ double cmi_max(double a, double b) { return b > a ? b : a; }
+
+template <bool CLAB>
+__global__ __launch_bounds__(256) void cmi_radius_kernel(const double* __restrict__ Z, int ld, int d, int n, const double* __restrict__ Y,
+                                                         int q, const double* __restrict__ C, int p, const int* __restrict__ lab, int k,
+                                                         int ch, long long rpad, u64* __restrict__ part_key, int* __restrict__ part_idx) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  const MiBuf buf(lds + CMI_KEY);
+  double* cy = lds + CMI_Y;
+  double* cc = lds + CMI_C;
+  int* clab = reinterpret_cast<int*>(lds + CMI_LAB);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long long r0 = (long long)blockIdx.x * HR;
+  const long long r = r0 + lane;
+  const bool ok = r < n;
+  const int t_lo = (int)blockIdx.y * ch, t_hi = min(((int)blockIdx.y + 1) * ch, pair_tile_count(n));
+  double my[SVAE_MI_MAX_Y] = {0.0, 0.0, 0.0, 0.0}, mc[SVAE_CMI_MAX_C] = {0.0, 0.0, 0.0, 0.0};
+  int mylab = 0;
+#pragma unroll
+  for (int f = 0; f < SVAE_MI_MAX_Y; ++f) {
+    if (ok && f < q) my[f] = Y[r * q + f];
+    if (!CLAB && ok && f < p) mc[f] = C[r * p + f];
+  }
+  if (CLAB && ok) mylab = lab[r];
+  const PairRows rows = pair_rows(Z, ld, d, n, r0, lds + PAIR_LDS_QS, lds + PAIR_LDS_CS);
+  u64 thr = buf.reset(ok, lane);
+  for (int ct = t_lo; ct < t_hi; ++ct) {
+    const long long c0 = (long long)ct * HT;
+    mi_stage_y(Y, q, n, c0, cy);
+    if (CLAB) {
+      if (threadIdx.x < HT) clab[threadIdx.x] = c0 + threadIdx.x < n ? lab[c0 + threadIdx.x] : 0;
+    } else {
+      mi_stage_y(C, p, n, c0, cc);
+    }
+    double s[HQ];
+    pair_tile(rows, c0, s);  // its first barrier also ends the setup above and the previous tile's cut
+#pragma unroll
+    for (int c4 = 0; c4 < HQ; ++c4) {
+      const int cl = wave * HQ + c4;
+      double m = cmi_max(s[c4], mi_sy(my, cy, cl));
+      if (!CLAB) m = cmi_max(m, mi_sy(mc, cc, cl));
+      const u64 key = cmi_bits(m);
+      if (key < thr) {
+        const long long c = c0 + cl;
+        if (c < n && c != r && (!CLAB || clab[cl] == mylab)) buf.append(lane, key, (int)c);
+      }
+    }
+    __syncthreads();
+    if (buf.could_overflow(lane)) {
+      buf.cut(k, lane, wave);
+      thr = buf.ths[lane];
+    }
+  }
+  __syncthreads();  // an empty tile range comes here straight from the setup
+  buf.cut(k, lane, wave);
+  if (ok) buf.write_sorted(k, lane, wave, part_key + ((long long)blockIdx.y * rpad + r) * k, part_idx + ((long long)blockIdx.y * rpad + r) * k);
+}
+
+// nzc, nyc and nc are zero on entry; every block adds the counts of its rows over its column tiles
+template <bool CLAB>
+__global__ __launch_bounds__(256) void cmi_count_kernel(const double* __restrict__ Z, int ld, int d, int n, const double* __restrict__ Y,
+                                                        int q, const double* __restrict__ C, int p, const int* __restrict__ lab,
+                                                        const double* __restrict__ rho2, int ch, int* __restrict__ nzc,
+                                                        int* __restrict__ nyc, int* __restrict__ nc) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  double* cy = lds + CMI_Y;
+  double* cc = lds + CMI_C;
+  int* clab = reinterpret_cast<int*>(lds + CMI_LAB);
+  int* cnt = reinterpret_cast<int*>(lds + CMI_CNT);  // [which][wave][lane]
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const PairTileRange tr = pair_chunk_tiles(n, ch);
+  const long long r = tr.r0 + lane;
+  const bool ok = r < n;
+  const u64 rb = ok ? cmi_bits(rho2[r]) : 0ull;  // a lane past n counts nothing
+  double my[SVAE_MI_MAX_Y] = {0.0, 0.0, 0.0, 0.0}, mc[SVAE_CMI_MAX_C] = {0.0, 0.0, 0.0, 0.0};
+  int mylab = 0;
+#pragma unroll
+  for (int f = 0; f < SVAE_MI_MAX_Y; ++f) {
+    if (ok && f < q) my[f] = Y[r * q + f];
+    if (!CLAB && ok && f < p) mc[f] = C[r * p + f];
+  }
+  if (CLAB && ok) mylab = lab[r];
+  const PairRows rows = pair_rows(Z, ld, d, n, tr.r0, lds + PAIR_LDS_QS, lds + PAIR_LDS_CS);
+  int azc = 0, ayc = 0, ac = 0;
+  for (int ct = tr.t_lo; ct < tr.t_hi; ++ct) {
+    const long long c0 = (long long)ct * HT;
+    mi_stage_y(Y, q, n, c0, cy);
+    if (CLAB) {
+      if (threadIdx.x < HT) clab[threadIdx.x] = c0 + threadIdx.x < n ? lab[c0 + threadIdx.x] : 0;
+    } else {
+      mi_stage_y(C, p, n, c0, cc);
+    }
+    double s[HQ];
+    pair_tile(rows, c0, s);
+#pragma unroll
+    for (int c4 = 0; c4 < HQ; ++c4) {
+      const int cl = wave * HQ + c4;
+      const long long c = c0 + cl;
+      const double sy = mi_sy(my, cy, cl);
+      if (CLAB) {
+        const bool live = c < n && c != r && clab[cl] == mylab;
+        azc += live && cmi_bits(s[c4]) < rb ? 1 : 0;
+        ayc += live && cmi_bits(sy) < rb ? 1 : 0;
+      } else {
+        const bool live = c < n && c != r;
+        const double sc = mi_sy(mc, cc, cl);
+        azc += live && cmi_bits(cmi_max(s[c4], sc)) < rb ? 1 : 0;
+        ayc += live && cmi_bits(cmi_max(sy, sc)) < rb ? 1 : 0;
+        ac += live && cmi_bits(sc) < rb ? 1 : 0;
+      }
+    }
+    __syncthreads();  // the reads of cy, cc and clab end here; the next tile stages them again
+  }
+  cnt[wave * HR + lane] = azc;
+  cnt[(4 + wave) * HR + lane] = ayc;
+  cnt[(8 + wave) * HR + lane] = ac;
+  __syncthreads();
+  if (wave == 0 && ok) {
+    atomicAdd(&nzc[r], ((cnt[lane] + cnt[HR + lane]) + cnt[2 * HR + lane]) + cnt[3 * HR + lane]);
+    atomicAdd(&nyc[r], ((cnt[4 * HR + lane] + cnt[5 * HR + lane]) + cnt[6 * HR + lane]) + cnt[7 * HR + lane]);
+    if (!CLAB) atomicAdd(&nc[r], ((cnt[8 * HR + lane] + cnt[9 * HR + lane]) + cnt[10 * HR + lane]) + cnt[11 * HR + lane]);
+  }
+}
+
+// The draw of the local permutation null (Runge 2018): block b is one wave and draws permutation b.  Rows are visited in the
+// order order[b][0..n); lane e holds the row's e-th scanned donor j = nbr[i][scan[b][i][e]] and its bit of the used-bitmap in LDS;
+// one ballot picks the first unused donor in scan order, or the last one tried when all kp are used.  One wave-step per row.  An
+// entry out of range reads and marks nothing: a row index past n skips the visit, a donor past n counts as used.
+constexpr int CMI_PERM_MAX_N = 1 << 19;  // the bitmap: n / 8 bytes, at most 64 KiB
+__global__ __launch_bounds__(64) void cmi_local_perm_kernel(const int* __restrict__ nbr, int n, int kp, const int* __restrict__ order,
+                                                            const unsigned char* __restrict__ scan, int* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned used[];
+  const int lane = threadIdx.x;
+  const int words = (n + 31) >> 5;
+  for (int w = lane; w < words; w += 64) used[w] = 0u;
+  const int* ord = order + (long long)blockIdx.x * n;
+  const unsigned char* sc = scan + (long long)blockIdx.x * n * kp;
+  int* o = out + (long long)blockIdx.x * n;
+  // the candidate of this lane for visit t: independent of the bitmap, so the loads of visit t + 1 are issued before visit t ends
+  auto candidate = [&](int t, int* i_out) {
+    int j = -1;
+    const int i = t < n ? ord[t] : -1;
+    if (i >= 0 && i < n && lane < kp) {
+      const int pos = min((int)sc[(long long)i * kp + lane], kp - 1);
+      j = nbr[(long long)i * kp + pos];
+    }
+    *i_out = i;
+    return j;
+  };
+  int i, j = candidate(0, &i);
+  for (int t = 0; t < n; ++t) {
+    int i2;
+    const int j2 = candidate(t + 1, &i2);
+    __syncthreads();  // one wave: orders the bitmap write of the previous visit (and the zeroing) before this read
+    const bool in = j >= 0 && j < n;
+    const bool free_ = lane < kp && in && !((used[in ? j >> 5 : 0] >> (j & 31)) & 1u);
+    const unsigned long long mask = __ballot(free_);
+    const int pick = mask ? __ffsll((long long)mask) - 1 : kp - 1;
+    const int jp = __shfl(j, pick);
+    if (lane == 0 && i >= 0 && i < n) {
+      o[i] = jp;
+      if (jp >= 0 && jp < n) used[jp >> 5] |= 1u << (jp & 31);
+    }
+    i = i2;
+    j = j2;
+  }
+}
+
 }  // namespace svae
 
 using namespace svae;
@@ -278,4 +471,73 @@ extern "C" int svae_mi_psi_sums(const int* a, const int* b, long long n, double*
   SVAE_REQUIRE(a && out && n >= 1, SVAE_ERR_ARG, "mi_psi_sums: bad args (n=%lld)", n);
   hipLaunchKernelGGL(mi_psi_sums_kernel, dim3(b ? 2 : 1), dim3(256), 0, ST(stream), a, b, n, out);
   return check_launch("mi_psi_sums");
+}
+
+// the checks that svae_cmi_radius and svae_cmi_counts share
+static int cmi_check_rows(const char* what, const double* Z, int ld, int d, int n, const double* Y, int q, const double* C, int p,
+                          const int* clab) {
+  if (int e = check_pair_rows(what, Z, ld, d, n, 2)) return e;
+  SVAE_REQUIRE(Y != nullptr, SVAE_ERR_ARG, "%s: null argument (Y)", what);
+  SVAE_REQUIRE(q >= 1 && q <= SVAE_MI_MAX_Y, SVAE_ERR_ARG, "%s: bad width of y (q=%d, at most %d)", what, q, SVAE_MI_MAX_Y);
+  SVAE_REQUIRE((C != nullptr) != (clab != nullptr), SVAE_ERR_ARG, "%s: exactly one of C and clab must be given", what);
+  SVAE_REQUIRE(clab || (p >= 1 && p <= SVAE_CMI_MAX_C), SVAE_ERR_ARG, "%s: bad width of c (p=%d, at most %d)", what, p, SVAE_CMI_MAX_C);
+  return SVAE_OK;
+}
+
+extern "C" int svae_cmi_radius(const double* Z, int ld, int d, int n, const double* Y, int q, const double* C, int p, const int* clab,
+                               int k, void* work, double* rho2, void* stream) {
+  if (int e = cmi_check_rows("cmi_radius", Z, ld, d, n, Y, q, C, p, clab)) return e;
+  SVAE_REQUIRE(mi_sizes_ok(n, k), SVAE_ERR_ARG, "cmi_radius: bad neighbour count (k=%d n=%d, at most %d)", k, n, SVAE_MI_MAX_K);
+  SVAE_REQUIRE(work && rho2, SVAE_ERR_ARG, "cmi_radius: null argument");
+  const KnnPlan pl = mi_plan(n);
+  KnnLists l;
+  if (int e = knn_work_lists("cmi_radius", work, pl, k, &l)) return e;
+  if (clab) {
+    static DeviceOnce once;
+    if (int e = allow_lds(cmi_radius_kernel<true>, once, (int)CMI_RADIUS_LDS, "cmi_radius")) return e;
+    hipLaunchKernelGGL(cmi_radius_kernel<true>, dim3(pl.gx, pl.gy), dim3(256), CMI_RADIUS_LDS, ST(stream), Z, ld, d, n, Y, q, C, p, clab, k,
+                       pl.ch, pl.rpad, l.key, l.idx);
+  } else {
+    static DeviceOnce once;
+    if (int e = allow_lds(cmi_radius_kernel<false>, once, (int)CMI_RADIUS_LDS, "cmi_radius")) return e;
+    hipLaunchKernelGGL(cmi_radius_kernel<false>, dim3(pl.gx, pl.gy), dim3(256), CMI_RADIUS_LDS, ST(stream), Z, ld, d, n, Y, q, C, p, clab, k,
+                       pl.ch, pl.rpad, l.key, l.idx);
+  }
+  if (int e = check_launch("cmi_radius")) return e;
+  const long long cells = (long long)n * k;
+  hipLaunchKernelGGL(mi_finish_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, ST(stream), l.key, l.idx, (int)pl.gy, pl.rpad,
+                     n, k, (const int*)nullptr, rho2);
+  return check_launch("cmi_finish");
+}
+
+extern "C" int svae_cmi_counts(const double* Z, int ld, int d, int n, const double* Y, int q, const double* C, int p, const int* clab,
+                               const double* rho2, int* nzc, int* nyc, int* nc, void* stream) {
+  if (int e = cmi_check_rows("cmi_counts", Z, ld, d, n, Y, q, C, p, clab)) return e;
+  SVAE_REQUIRE((C != nullptr) == (nc != nullptr), SVAE_ERR_ARG, "cmi_counts: nc belongs to C (with clab the class size is the host's)");
+  SVAE_REQUIRE(rho2 && nzc && nyc, SVAE_ERR_ARG, "cmi_counts: null argument");
+  const KnnPlan pl = mi_plan(n);
+  hipError_t err = hipMemsetAsync(nzc, 0, (size_t)n * sizeof(int), ST(stream));
+  if (err == hipSuccess) err = hipMemsetAsync(nyc, 0, (size_t)n * sizeof(int), ST(stream));
+  if (err == hipSuccess && nc) err = hipMemsetAsync(nc, 0, (size_t)n * sizeof(int), ST(stream));
+  SVAE_REQUIRE(err == hipSuccess, SVAE_ERR_LAUNCH, "cmi_counts: hipMemsetAsync: %s", hipGetErrorString(err));
+  if (clab)
+    hipLaunchKernelGGL(cmi_count_kernel<true>, dim3(pl.gx, pl.gy), dim3(256), CMI_COUNT_LDS, ST(stream), Z, ld, d, n, Y, q, C, p, clab, rho2,
+                       pl.ch, nzc, nyc, nc);
+  else
+    hipLaunchKernelGGL(cmi_count_kernel<false>, dim3(pl.gx, pl.gy), dim3(256), CMI_COUNT_LDS, ST(stream), Z, ld, d, n, Y, q, C, p, clab, rho2,
+                       pl.ch, nzc, nyc, nc);
+  return check_launch("cmi_counts");
+}
+
+extern "C" int svae_local_permutations(const int* nbr, int n, int kp, const int* order, const unsigned char* scan, int P, int* out,
+                                       void* stream) {
+  SVAE_REQUIRE(nbr && order && scan && out, SVAE_ERR_ARG, "local_permutations: null argument");
+  SVAE_REQUIRE(n >= 1 && n <= CMI_PERM_MAX_N, SVAE_ERR_ARG, "local_permutations: bad row count (n=%d, at most %d)", n, CMI_PERM_MAX_N);
+  SVAE_REQUIRE(kp >= 1 && kp <= SVAE_CMI_MAX_DONORS, SVAE_ERR_ARG, "local_permutations: bad donor count (kp=%d, at most %d)", kp,
+               SVAE_CMI_MAX_DONORS);
+  SVAE_REQUIRE(P >= 1 && P <= SVAE_MMD_NULL_MAX, SVAE_ERR_ARG, "local_permutations: bad permutation count (P=%d, at most %d)", P,
+               SVAE_MMD_NULL_MAX);
+  const size_t lds = (size_t)((n + 31) / 32) * sizeof(unsigned);  // at most 64 KiB: the default dynamic LDS limit
+  hipLaunchKernelGGL(cmi_local_perm_kernel, dim3((unsigned)P), dim3(64), lds, ST(stream), nbr, n, kp, order, scan, out);
+  return check_launch("local_permutations");
 }

@@ -1,4 +1,6 @@
 from .cluster import GaussianMixture, KMeans, dbscan, gmm, kmeans  # noqa: F401
+from .conditional_mi import (conditional_mutual_information, conditional_mutual_information_permutation_test,  # noqa: F401
+                             conditional_permutations)
 from .density import DensityGrid, DensityMap, density_map, density_regions  # noqa: F401
 from .embed import TSNE, tsne, tsne_affinities  # noqa: F401
 from .embed_transform import TSNEMap, tsne_transform  # noqa: F401

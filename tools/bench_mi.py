@@ -9,9 +9,15 @@ centres, k = 3, inputs already on the device, synchronised host clock, after a w
   buffer       (host, numpy, --buffer) the share of a row tile's candidates that reach the LDS buffer of mi_radius_kernel, over
                the first 4 column tiles and over the rest, by replaying the kernel's append and cut rule on rows 0..63
 
+  conditional  (--conditional, instead of the above) the radius and count passes of conditional_mutual_information with a real c
+               next to those of mutual_information at the same n, d, k and y (the four passes timed in turn, 9 times each; the
+               median, and the largest (max - min) / median of the four), the whole conditional call, and
+               conditional_permutations for 64 permutations of --draw-rows rows at 8 donors
+
 Prints one JSON line.
 
-    python tools/bench_mi.py [--sizes 5000,20000,50000] [--dim 32] [--perms 200] [--reference] [--buffer]"""
+    python tools/bench_mi.py [--sizes 5000,20000,50000] [--dim 32] [--perms 200] [--reference] [--buffer]
+    python tools/bench_mi.py --conditional [--sizes 5000,20000,50000] [--dim 32] [--draw-rows 20000]"""
 import argparse
 import json
 import os
@@ -121,6 +127,58 @@ def buffer_share(z, y, k, cap=128, first=4):
                 cuts=cuts, tiles=t + 1)
 
 
+def conditional(z, y, c, repeats=9):
+    """z on the device, y [n, 3] and c [n] real -> the radius and count passes of conditional_mutual_information next to those of
+    mutual_information on the same z, y and k (the median of `repeats` synchronised host-clock timings each, after one untimed
+    call, the four in turn) and the whole conditional call"""
+    from scrubvae_amd.eval import conditional_mi as CM
+    dev = z.device
+    with torch.cuda.device(dev):
+        cr = CM._CmiRun(CM._cmi_check(z, y, c, K), dev)
+        mr = MI._MiRun(MI._mi_check(z, y, K), dev)
+        lib, st = cr.lib, cr.st
+        same = (cr.Z.data_ptr(), cr.ld, cr.ld, cr.n, cr.Y.data_ptr(), cr.q)   # z and y are one set of rows for the four passes
+        calls = dict(
+            cmi_radius=lambda: lib.svae_cmi_radius(*same, cr.C.data_ptr(), cr.p, None, K, cr.work.data_ptr(), cr.rho2.data_ptr(), st),
+            cmi_counts=lambda: lib.svae_cmi_counts(*same, cr.C.data_ptr(), cr.p, None, cr.rho2.data_ptr(), cr.nzc.data_ptr(),
+                                                   cr.nyc.data_ptr(), cr.nc.data_ptr(), st),
+            mi_radius=lambda: lib.svae_mi_radius(*same, None, None, K, mr.work.data_ptr(), mr.rho2.data_ptr(), st),
+            mi_counts=lambda: lib.svae_mi_counts(*same, mr.rho2.data_ptr(), mr.nz.data_ptr(), mr.ny.data_ptr(), st))
+        took = {name: [] for name in calls}
+        for name, call in calls.items():
+            MI.check(call())
+        for _ in range(repeats):                      # the four passes in turn, so that a busy host touches all of them alike
+            for name, call in calls.items():
+                t0 = _clock(dev)
+                MI.check(call())
+                took[name].append(_clock(dev) - t0)
+        times = {name: float(np.median(t)) for name, t in took.items()}
+        spread = max((max(t) - min(t)) / np.median(t) for t in took.values())
+        t0 = _clock(dev)
+        value = CM.conditional_mutual_information(z, y, c, n_neighbors=K)
+        whole = _clock(dev) - t0
+    row = {f"{name}_s": round(t, 5) for name, t in times.items()}
+    row.update(value=round(value, 6), whole_s=round(whole, 5), radius_ratio=round(times["cmi_radius"] / times["mi_radius"], 3),
+               counts_ratio=round(times["cmi_counts"] / times["mi_counts"], 3), largest_spread=round(float(spread), 3))
+    return row
+
+
+def local_draw(c, P=64, donors=8, repeats=5):
+    """conditional_permutations(c, P) of a real c [n] on the device: the median of `repeats` timings after one untimed call, and
+    the share of the drawn entries whose donor had served already"""
+    from scrubvae_amd.eval import conditional_mi as CM
+    cd = torch.as_tensor(c).cuda()
+    CM.conditional_permutations(cd, P, n_donors=donors, seed=0)      # untimed: torch's sort and random kernels, svae_knn
+    took = []
+    for r in range(repeats):
+        t0 = _clock(cd.device)
+        perms = CM.conditional_permutations(cd, P, n_donors=donors, seed=r)
+        took.append(_clock(cd.device) - t0)
+    repeated = float((perms.sort(dim=1).values.diff(dim=1) == 0).sum()) / perms.numel()
+    return dict(n=len(cd), P=P, n_donors=donors, draw_s=round(float(np.median(took)), 4), slowest_s=round(max(took), 4),
+                repeated_share=round(repeated, 4))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="5000,20000,50000")
@@ -128,8 +186,24 @@ def main():
     ap.add_argument("--perms", type=int, default=200)
     ap.add_argument("--reference", action="store_true")
     ap.add_argument("--buffer", action="store_true")
+    ap.add_argument("--conditional", action="store_true")
+    ap.add_argument("--draw-rows", type=int, default=20000)
     a = ap.parse_args()
     sizes = [int(s) for s in a.sizes.split(",") if s]
+    if a.conditional:
+        out = dict(device=torch.cuda.get_device_name(0), d=a.dim, k=K, conditional=[])
+        condition = lambda z, n: (0.7 * z[:, 0] + 0.7 * np.random.default_rng(1).normal(size=n)).astype(np.float32)
+        z, y, _ = rows(min(sizes), a.dim)
+        conditional(torch.from_numpy(z).cuda(), y, condition(z, len(z)), repeats=1)   # warm-up: code objects, torch kernels
+        for n in sizes:
+            z, y, _ = rows(n, a.dim)
+            row = dict(n=n, **conditional(torch.from_numpy(z).cuda(), y, condition(z, n)))
+            out["conditional"].append(row)
+            print(json.dumps(row), file=sys.stderr, flush=True)
+        z = rows(a.draw_rows, a.dim)[0]
+        out["local_draw"] = local_draw(condition(z, a.draw_rows))
+        print(json.dumps(out))
+        return
     z, y, lab = rows(min(sizes), a.dim)
     MI.mutual_information(torch.from_numpy(z).cuda(), y, n_neighbors=K)          # warm-up: code objects, torch kernels
     MI.mutual_information(torch.from_numpy(z).cuda(), lab, n_neighbors=K)
