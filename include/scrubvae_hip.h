@@ -958,6 +958,34 @@ long long svae_density_work(int n, int gx, int gy);
 int svae_density_grid(const double* Y, int ld, int n, const double* h_rows /* NULL: use h */, double h, double x0, double dx, int gx,
                       double y0, double dy, int gy, void* work, double* D, void* stream);
 
+/* ------------------------------------------------------- Entropic optimal transport between latent sets (csrc/ot.hip) -------- */
+/* The two passes of a log-domain Sinkhorn solve between the query rows Q [m][ldq] and the candidate rows X [n][ldx], both fp64 of
+ * d >= 1 features, 1 <= m, n < 2^26; nothing of size m x n is stored and every result is bit-reproducible.  With s_ij the squared
+ * distance of csrc/pair_tiles.h (feature order, no FMA), the cost is c_ij = s_ij for kind = 0 (squared Euclidean) or the correctly
+ * rounded sqrt(s_ij) for kind = 1 (Euclidean), and for the column offsets u [n] (finite)
+ *     v_ij = u_j - c_ij * inv_eps,        inv_eps = the host's 1.0 / eps, finite and > 0: one product per pair, no division.
+ *
+ * svae_ot_softmin: L [m], L_i = log sum_j exp(v_ij) over all j < n, and with cbar [m] non-null
+ * cbar_i = (sum_j exp(v_ij) c_ij) / (sum_j exp(v_ij)).  A streaming log-sum-exp: a thread (one query row, 16 candidates of every
+ * 64-column tile) keeps a running maximum M and the sums scaled by exp(-M), rescaled once per tile; the (M, S) pairs of the four
+ * waves merge as ((w0, w1), w2), w3 and those of the column chunks in chunk order, M = max, S = S1 exp(M1 - M) + S2 exp(M2 - M),
+ * L = M + log(S).  The column chunks follow the rule of svae_knn_cross (at most 8, 1 once the grid holds 512 blocks; row tiles
+ * counted from m, column tiles from n), so the order of every sum is a function of (m, n) alone.  A row's L does not depend on
+ * the other rows of Q.  work: svae_ot_softmin_work doubles (0 for sizes out of range): 3 x column chunks x m padded to 64.
+ *
+ * svae_ot_apply: out [m][ldo], out_i = sum_j exp(v_ij - L_i) V_j for the c columns of V [n][ldv], 1 <= c <= SVAE_OT_MAX_COLS.
+ * With L = svae_ot_softmin's of the same arguments this is the row-normalised transport plan times V; the weights lie in [0, 1]
+ * up to rounding whatever the potentials.  The 64 x 64 tiles of weights are multiplied with V's rows on the fp64 matrix cores;
+ * the chunks' partials are added in chunk order.  work: svae_ot_apply_work doubles (0 for sizes or c out of range): column
+ * chunks x m padded to 64 x c padded to 16, 64 or 128. */
+#define SVAE_OT_MAX_COLS 128
+long long svae_ot_softmin_work(int m, int n);
+int svae_ot_softmin(const double* Q, int ldq, int m, const double* X, int ldx, int n, int d, const double* u, double inv_eps, int kind,
+                    double* work, double* L, double* cbar /* nullable */, void* stream);
+long long svae_ot_apply_work(int m, int n, int c);
+int svae_ot_apply(const double* Q, int ldq, int m, const double* X, int ldx, int n, int d, const double* u, double inv_eps, int kind,
+                  const double* L, const double* V, int ldv, int c, double* work, double* out, int ldo, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -237,6 +237,10 @@ SIGNATURES = {
     "svae_rank_curves": (I, [P, I, I, I, P, P, P, P]),
     "svae_density_work": (LL, [I, I, I]),
     "svae_density_grid": (I, [P, I, I, P, D, D, D, I, D, D, I, P, P, P]),
+    "svae_ot_softmin_work": (LL, [I, I]),
+    "svae_ot_softmin": (I, [P, I, I, P, I, I, I, P, D, I, P, P, P, P]),
+    "svae_ot_apply_work": (LL, [I, I, I]),
+    "svae_ot_apply": (I, [P, I, I, P, I, I, I, P, D, I, P, P, I, I, P, P, I, P]),
 }
 
 _lib = None
@@ -279,6 +283,7 @@ MI_MAX_K, MI_MAX_Y = 32, 4  # include/scrubvae_hip.h SVAE_MI_*
 CMI_MAX_C, CMI_MAX_DONORS = 4, 64  # include/scrubvae_hip.h SVAE_CMI_*
 TSNE_SEARCH_STEPS, TSNE_MAX_CHUNKS = 100, 8  # include/scrubvae_hip.h SVAE_TSNE_*
 DENSITY_MAX_GRID = 1024  # include/scrubvae_hip.h SVAE_DENSITY_MAX_GRID
+OT_MAX_COLS = 128  # include/scrubvae_hip.h SVAE_OT_MAX_COLS
 HSIC_MAX_Y, HSIC_PERMS = 4, 16  # include/scrubvae_hip.h SVAE_HSIC_*
 MAX_LOSS_TERMS = 48  # include/scrubvae_hip.h SVAE_MAX_LOSS_TERMS
 ERR_SHAPE, ERR_ALIGN, ERR_WORKSPACE, ERR_LAUNCH, ERR_ARG = -1, -2, -3, -4, -5  # include/scrubvae_hip.h svae_status

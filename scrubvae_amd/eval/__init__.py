@@ -14,3 +14,4 @@ from .metrics import (cluster_entropy, hungarian_match, knn_class_rand_cv, knn_r
 from .mutual_info import MIPermutationResult, latent_mi_scores, mutual_information, mutual_information_permutation_test  # noqa: F401
 from .neighbors import kneighbors, kneighbors_cross, kneighbors_graph, knn_label_purity, knn_transfer_labels  # noqa: F401
 from .silhouette import cluster_medoids, cluster_silhouette, silhouette_samples, silhouette_score  # noqa: F401
+from .transport import SinkhornDivergence, SinkhornResult, sinkhorn, sinkhorn_divergence, transport_flow  # noqa: F401
