@@ -793,11 +793,14 @@ __global__ __launch_bounds__(256) void ce_sum_kernel(const float* __restrict__ l
     for (int c = 1; c < C; ++c) mx = fmaxf(mx, x[c]);
     float se = 0.f;
     for (int c = 0; c < C; ++c) se += expf(x[c] - mx);
-    const float lse = mx + logf(se);
+    // everything relative to mx: mx + logf(se) rounds at the magnitude of the logits (ulp(100) = 7.6e-6), and expf(x - lse) turns that
+    // absolute error into a relative error of the softmax; expf(x - mx) / se and logf(se) - (x[y] - mx) stay at 2^-24
     const int y = labels[r];
-    loss = lse - x[y];
-    if (dlogits)
-      for (int c = 0; c < C; ++c) dlogits[(long long)r * ld + c] = scale * (expf(x[c] - lse) - (c == y ? 1.f : 0.f));
+    loss = logf(se) - (x[y] - mx);
+    if (dlogits) {
+      const float inv = 1.f / se;
+      for (int c = 0; c < C; ++c) dlogits[(long long)r * ld + c] = scale * (expf(x[c] - mx) * inv - (c == y ? 1.f : 0.f));
+    }
   }
   const float t = block_sum_256(loss, red4);
   if (threadIdx.x == 0) part[blockIdx.x] = t;
@@ -1055,21 +1058,21 @@ extern "C" int svae_rowloss_blocks(int rows) { return (rows + 255) / 256; }
 
 extern "C" int svae_mse_sum(const float* pred, int ld, const float* target, int ld_t, int rows, int C, float scale, float* part,
                             float* dpred, void* stream) {
-  SVAE_REQUIRE(pred && target && part && rows > 0 && C > 0, SVAE_ERR_ARG, "mse_sum: bad args");
+  SVAE_REQUIRE(pred && target && part && rows > 0 && C > 0 && ld >= C && ld_t >= C, SVAE_ERR_ARG, "mse_sum: bad args");
   hipLaunchKernelGGL(mse_sum_kernel, dim3(svae_rowloss_blocks(rows)), dim3(256), 0, ST(stream), pred, ld, target, ld_t, rows, C,
                      scale, part, dpred);
   return check_launch("mse_sum");
 }
 extern "C" int svae_ce_sum(const float* logits, int ld, const int* labels, int rows, int C, float scale, float* part,
                            float* dlogits, void* stream) {
-  SVAE_REQUIRE(logits && labels && part && rows > 0 && C > 0, SVAE_ERR_ARG, "ce_sum: bad args");
+  SVAE_REQUIRE(logits && labels && part && rows > 0 && C > 0 && ld >= C, SVAE_ERR_ARG, "ce_sum: bad args");
   hipLaunchKernelGGL(ce_sum_kernel, dim3(svae_rowloss_blocks(rows)), dim3(256), 0, ST(stream), logits, ld, labels, rows, C, scale,
                      part, dlogits);
   return check_launch("ce_sum");
 }
 extern "C" int svae_double_softmax_ce_sum(const float* logits, int ld, int rows, float scale, float* part, float* dlogits,
                                           void* stream) {
-  SVAE_REQUIRE(logits && part && rows > 0 && rows % 2 == 0, SVAE_ERR_ARG, "double_softmax_ce_sum: bad args");
+  SVAE_REQUIRE(logits && part && rows > 0 && rows % 2 == 0 && ld >= 2, SVAE_ERR_ARG, "double_softmax_ce_sum: bad args");
   hipLaunchKernelGGL(double_softmax_ce_kernel, dim3(svae_rowloss_blocks(rows)), dim3(256), 0, ST(stream), logits, ld, rows, scale,
                      part, dlogits);
   return check_launch("double_softmax_ce_sum");

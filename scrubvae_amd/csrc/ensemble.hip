@@ -314,11 +314,12 @@ __global__ __launch_bounds__(256) void ens_loss_kernel(const EnsLossArgs a) {
         for (int c = 1; c < a.C; ++c) mx = fmaxf(mx, x[c]);
         float se = 0.f;
         for (int c = 0; c < a.C; ++c) se += expf(x[c] - mx);
-        const float lse = mx + logf(se);
-        const int y = a.labels[r];
-        loss = lse - x[y];
-        if (d)
-          for (int c = 0; c < a.C; ++c) d[c] = gs * (expf(x[c] - lse) - (c == y ? 1.f : 0.f));
+        const int y = a.labels[r];  // relative to mx, as ce_sum_kernel: no rounding at the magnitude of the logits
+        loss = logf(se) - (x[y] - mx);
+        if (d) {
+          const float inv = 1.f / se;
+          for (int c = 0; c < a.C; ++c) d[c] = gs * (expf(x[c] - mx) * inv - (c == y ? 1.f : 0.f));
+        }
       } else {
         const float x0 = x[0], x1 = x[1];
         const float mx = fmaxf(x0, x1);

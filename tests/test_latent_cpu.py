@@ -127,10 +127,6 @@ ALLOWED_UNTESTED = {
     "linear_weight_from_tio": "weight-layout converter (host tensor ops), no kernel",
     "kde_mi": "driven through model/disentangle.py's MutInfoEstimator by test_kde_mi_vs_fp64",
     "kde_mi_autograd": "driven through model/disentangle.py's MutInfoEstimator by test_kde_mi_vs_fp64",
-    "ens_fwd": "driven through model/disentangle.py by test_fused_ensemble_fwd_bwd",
-    "ens_bwd": "driven through model/disentangle.py by test_fused_ensemble_fwd_bwd",
-    "ens_bwd_workspace": "driven through model/disentangle.py by test_fused_ensemble_fwd_bwd",
-    "ens_loss": "driven through model/disentangle.py by test_fused_ensemble_fwd_bwd",
 }
 
 
