@@ -627,6 +627,55 @@ int svae_gmm_mstep_f64(const double* A, int lda, int d, int n, int K, int diag, 
 int svae_gmm_precision_f64(const double* L, const int* rank, const double* w, int d, int K, int ldp, double* P, double* cst, int* bad,
                            void* stream);
 
+/* ------------------------------------------------------------- Gaussian hidden Markov model (csrc/hmm.hip) --- */
+/* Scaled forward-backward pass of a K-state HMM over n frames, parallel in time and exact, and Viterbi decoding; fp64.
+ * B [K][ldb] = the resp of svae_gmm_estep_f64 run with unit weights (cst = log det P - d log(2 pi) / 2): the emission densities of
+ * every frame scaled to sum to 1 (exact zeros allowed), lpn [n] = the log of that scale; startprob [K]; transmat [K][K], rows sum
+ * to 1, zeros allowed.  K <= SVAE_HMM_MAX_STATES, n < 2^26.  The host cuts every sequence into segments of L = svae_hmm_segment(K)
+ * frames (a function of K alone; the last segment of a sequence is shorter), never across a sequence boundary:
+ *   seg [nseg][4] int = {first frame, frames, 1 for the first segment of its sequence else 0, sequence}
+ *   seq [nseq][4] int = {first segment, segments, first frame, frames}
+ * (device arrays; a table that does not fit n makes no access outside the arrays; seg[.][3] is the host's, no kernel reads it, and
+ * every entry point takes both tables so that they are called alike: transfer reads seg only).  States are padded to KP = svae_hmm_padded(K)
+ * in {16, 32, 64}.  work holds svae_hmm_work(K, nseg) doubles: the transfer matrices [nseg][KP][KP] with their row exponents, the
+ * boundary vectors, the per-segment log-likelihoods and svae_hmm_xi_blocks(nseg) partials [KP][KP] of the transition counts.
+ * Nothing of size n x K^2 is stored.  No floating-point atomics and every sum in a fixed order: all outputs are bit-reproducible,
+ * and alpha, gamma and c of a sequence do not depend on the other sequences of the call or on their order (Xi, start_post and
+ * loglik are sums over the sequences in table order). */
+#define SVAE_HMM_MAX_STATES 64  /* = SVAE_GMM_MAX_COMPONENTS */
+#define SVAE_HMM_SEGMENT_16 512 /* L for KP = 16 */
+#define SVAE_HMM_SEGMENT_32 512 /* L for KP = 32 */
+#define SVAE_HMM_SEGMENT_64 512 /* L for KP = 64 */
+int svae_hmm_padded(int K);
+int svae_hmm_segment(int K);
+int svae_hmm_xi_blocks(int nseg);
+long long svae_hmm_work(int K, int nseg);
+/* Transfer: per segment T = prod_t transmat diag(b_t) (diag(b_1) first in the first segment of a sequence) as R [KP][KP] times one
+ * power of two per row (an integer exponent: the scaling rounds nothing), rescaled at every frame; R transmat runs on the fp64
+ * matrix cores.  A row whose sum reaches 0 stays 0. */
+int svae_hmm_transfer_f64(const double* B, long long ldb, int n, int K, const double* transmat, const int* seg, int nseg,
+                          const int* seq, int nseq, double* work, void* stream);
+/* Carry (after transfer): per sequence, the normalised forward vector entering every segment and the normalised backward vector at
+ * every segment's last frame, combined relative to the largest row exponent. */
+int svae_hmm_carry_f64(int n, int K, const double* startprob, const int* seg, int nseg, const int* seq, int nseq, double* work,
+                       void* stream);
+/* Fill (after carry): the scaled recursion inside every segment.  c [n] = the scale of every frame, gamma [K][n] = the smoothed
+ * posteriors (every column sums to 1; the buffer holds alpha between the two kernels; it must not be B),
+ * Xi [K][K] = sum_t alpha_{t-1}(i) transmat[i][j] b_t(j) beta_t(j) / c_t, start_post [K] = sum of gamma at the first frame of every
+ * sequence, loglik [1] = sum_t (log c_t + lpn_t). */
+int svae_hmm_fill_f64(const double* B, long long ldb, const double* lpn, int n, int K, const double* transmat, const int* seg, int nseg,
+                      const int* seq, int nseq, double* work, double* gamma, double* c, double* Xi, double* start_post, double* loglik,
+                      void* stream);
+/* transmat[i] = max(Xi[i] + transmat_prior - 1, 0) / its sum, startprob likewise from start_post; a row whose sum is 0 keeps its
+ * values. */
+int svae_hmm_update_f64(const double* Xi, const double* start_post, int K, double transmat_prior, double startprob_prior,
+                        double* transmat, double* startprob, void* stream);
+/* Viterbi: delta_t(j) = max_i (delta_{t-1}(i) + log_transmat[i][j]) + logB[j][t] with logB [K][n], one workgroup per sequence (only
+ * seq[.][2..3] are read), ties to the lower state at every step as np.argmax.  backptr [n][K] bytes (work), states [n],
+ * logprob [nseq] = the log-probability of each sequence's path.  Only adds and compares: equal to the same recursion in numpy. */
+int svae_hmm_viterbi(const double* log_startprob, const double* log_transmat, const double* logB, int n, int K, const int* seq,
+                     int nseq, unsigned char* backptr, int* states, double* logprob, void* stream);
+
 /* ---------------------------------------------------------------------- k-means clustering (csrc/kmeans.hip) --- */
 /* Lloyd's iteration of sklearn's KMeans(algorithm="lloyd"), fp64, on the centred rows A [n][lda] of svae_cv_center (as for the
  * mixture above: column d = 1) and centres C [K][ldc] in that centred frame.  d <= SVAE_CV_MAX_DIM, K <= SVAE_KMEANS_MAX_CLUSTERS.

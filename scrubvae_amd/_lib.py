@@ -241,6 +241,15 @@ SIGNATURES = {
     "svae_ot_softmin": (I, [P, I, I, P, I, I, I, P, D, I, P, P, P, P]),
     "svae_ot_apply_work": (LL, [I, I, I]),
     "svae_ot_apply": (I, [P, I, I, P, I, I, I, P, D, I, P, P, I, I, P, P, I, P]),
+    "svae_hmm_padded": (I, [I]),
+    "svae_hmm_segment": (I, [I]),
+    "svae_hmm_xi_blocks": (I, [I]),
+    "svae_hmm_work": (LL, [I, I]),
+    "svae_hmm_transfer_f64": (I, [P, LL, I, I, P, P, I, P, I, P, P]),
+    "svae_hmm_carry_f64": (I, [I, I, P, P, I, P, I, P, P]),
+    "svae_hmm_fill_f64": (I, [P, LL, P, I, I, P, P, I, P, I, P, P, P, P, P, P, P]),
+    "svae_hmm_update_f64": (I, [P, P, I, D, D, P, P, P]),
+    "svae_hmm_viterbi": (I, [P, P, P, I, I, P, I, P, P, P, P]),
 }
 
 _lib = None
@@ -284,6 +293,8 @@ CMI_MAX_C, CMI_MAX_DONORS = 4, 64  # include/scrubvae_hip.h SVAE_CMI_*
 TSNE_SEARCH_STEPS, TSNE_MAX_CHUNKS = 100, 8  # include/scrubvae_hip.h SVAE_TSNE_*
 DENSITY_MAX_GRID = 1024  # include/scrubvae_hip.h SVAE_DENSITY_MAX_GRID
 OT_MAX_COLS = 128  # include/scrubvae_hip.h SVAE_OT_MAX_COLS
+HMM_MAX_STATES = 64  # include/scrubvae_hip.h SVAE_HMM_MAX_STATES
+HMM_SEGMENT = {16: 512, 32: 512, 64: 512}  # include/scrubvae_hip.h SVAE_HMM_SEGMENT_16 / _32 / _64, by padded state count
 HSIC_MAX_Y, HSIC_PERMS = 4, 16  # include/scrubvae_hip.h SVAE_HSIC_*
 MAX_LOSS_TERMS = 48  # include/scrubvae_hip.h SVAE_MAX_LOSS_TERMS
 ERR_SHAPE, ERR_ALIGN, ERR_WORKSPACE, ERR_LAUNCH, ERR_ARG = -1, -2, -3, -4, -5  # include/scrubvae_hip.h svae_status

@@ -4,7 +4,7 @@ import subprocess
 import sys
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
-SOURCES = ["capi.hip", "gemm_f32.hip", "gemm_bf16s.hip", "halo_ws_bf16s.hip", "wgrad_bf16s.hip", "elementwise.hip", "pose_tail.hip", "latent.hip", "preprocess.hip", "ensemble.hip", "decode.hip", "gmm.hip", "kmeans.hip", "hdbscan.hip", "mmd.hip", "mmd_null.hip", "silhouette.hip", "knn.hip", "tsne.hip", "hsic.hip", "mi.hip", "rank.hip", "density.hip", "ot.hip"]
+SOURCES = ["capi.hip", "gemm_f32.hip", "gemm_bf16s.hip", "halo_ws_bf16s.hip", "wgrad_bf16s.hip", "elementwise.hip", "pose_tail.hip", "latent.hip", "preprocess.hip", "ensemble.hip", "decode.hip", "gmm.hip", "kmeans.hip", "hdbscan.hip", "mmd.hip", "mmd_null.hip", "silhouette.hip", "knn.hip", "tsne.hip", "hsic.hip", "mi.hip", "rank.hip", "density.hip", "ot.hip", "hmm.hip"]
 HEADERS = [os.path.join(CSRC, h) for h in ("svae_internal.h", "gemm_common.h", "split_common.h", "split_gather.h", "pair_tiles.h", "fixed_sum.h", "knn_buffer.h", "mmd_common.h", "hsic_common.h")]
 HEADERS.append(os.path.join(CSRC, "..", "..", "include", "scrubvae_hip.h"))
 OUT = os.path.join(CSRC, "libscrubvae_hip.so")

@@ -1,4 +1,5 @@
 from .cluster import GaussianMixture, KMeans, dbscan, gmm, kmeans  # noqa: F401
+from .hmm import GaussianHMM, dwell_times, hmm, state_runs  # noqa: F401
 from .conditional_mi import (conditional_mutual_information, conditional_mutual_information_permutation_test,  # noqa: F401
                              conditional_permutations)
 from .density import DensityGrid, DensityMap, density_map, density_regions  # noqa: F401

@@ -443,8 +443,8 @@ class _Fitted(GaussianMixture):
 
 
 def _as_device_model(model):
-    """model itself when it is a GaussianMixture or KMeans of this module, else a copy of sklearn's fitted attribute names of it"""
-    if isinstance(model, (GaussianMixture, KMeans)):
+    """model itself when it is a GaussianMixture or KMeans of this module (or a GaussianHMM of eval/hmm.py), else a copy of sklearn's fitted attribute names of it"""
+    if isinstance(model, (GaussianMixture, KMeans)) or getattr(model, "runs_on_device", False):
         return model
     if hasattr(model, "cluster_centers_"):
         m = KMeans(n_clusters=len(model.cluster_centers_))
@@ -464,6 +464,8 @@ def _check_model_exists(func):
     labels saved to {path}{label}_{name}.npy; an existing pickle is loaded, and its labels too when that file exists.  A pickle
     without a labels file predicts (the reference raises UnboundLocalError there)."""
 
+    what = getattr(func, "model_name", "GMM")  # the reference's messages say GMM
+
     @functools.wraps(func)
     def wrapper(latents, label="cluster", path=None, **kwargs):
         if path is None:
@@ -479,7 +481,7 @@ def _check_model_exists(func):
         else:
             model = func(latents=latents, **kwargs)
             if path is not None:
-                print("Saving GMM model")
+                print("Saving {} model".format(what))
                 with open(model_path, "wb") as f:
                     pickle.dump(model, f)
         if model_exists and Path(preds_path).exists():
@@ -487,9 +489,11 @@ def _check_model_exists(func):
             k_pred = np.load(preds_path)
         else:
             print("Calculating {} clusters on the device ...".format(func.__name__))
-            k_pred = _as_device_model(model).predict(latents)
+            # func.predict_keys: the arguments predict takes along with the latents (hmm(): the sequence lengths)
+            extra = {k: kwargs[k] for k in getattr(func, "predict_keys", ()) if k in kwargs}
+            k_pred = _as_device_model(model).predict(latents, **extra)
             if path is not None:
-                print("Saving GMM cluster predictions")
+                print("Saving {} cluster predictions".format(what))
                 np.save(preds_path, k_pred)
         return k_pred, model
 
