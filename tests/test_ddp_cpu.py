@@ -94,21 +94,6 @@ def test_gloo_world2_protocol():
     assert ok_bn and ok_grad
 
 
-def test_capi_exports_every_declared_symbol():
-    """The C-ABI library loads on a GPU-less host and exports every symbol include/*.h declares."""
-    import re
-    from scrubvae_amd import _lib
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    header = open(os.path.join(root, "include", "scrubvae_hip.h")).read()
-    declared = set(re.findall(r"\b(svae_[a-z0-9_]+)\s*\(", header))
-    declared -= {"svae_status"}
-    lib = _lib.lib()
-    for name in sorted(declared):
-        assert hasattr(lib, name), f"{name} declared in the header but not exported"
-        assert name in _lib.SIGNATURES, f"{name} has no ctypes signature in scrubvae_amd/_lib.py"
-    assert lib.svae_version() >= 100
-
-
 def test_product_never_imports_oracle():
     """oracle/ is test infrastructure: nothing under scrubvae_amd/ may import it."""
     root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "scrubvae_amd")

@@ -59,11 +59,7 @@ def test_cluster_entropy_equals_reference_loop():
 
 
 def test_abi_names_and_exports():
-    from scrubvae_amd import _lib
     import scrubvae_amd.eval as E
-    for name in ("svae_gmm_kpp_blocks", "svae_gmm_kpp_round", "svae_gmm_estep_blocks", "svae_gmm_estep_f64", "svae_gmm_sum_f64",
-                 "svae_gmm_chunks", "svae_gmm_mstep_f64", "svae_gmm_precision_f64"):
-        assert name in _lib.SIGNATURES
     for name in ("gmm", "GaussianMixture", "cluster_entropy"):
         assert callable(getattr(E, name))
 

@@ -152,10 +152,3 @@ def test_constructor_is_sklearns():
                 allow_single_cluster=False, store_centers=None, copy=False)
     assert [p for p in params if p != "self"] == list(want)
     assert all(params[k].default == v for k, v in want.items())
-
-
-def test_new_exports_have_signatures():
-    from scrubvae_amd import _lib
-    lib = _lib.lib()
-    for name in ("svae_hdb_core", "svae_hdb_boruvka", "svae_hdb_relabel", "svae_hdb_merge", "svae_hdb_tree", "svae_hdb_cut"):
-        assert name in _lib.SIGNATURES and hasattr(lib, name)

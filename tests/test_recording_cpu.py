@@ -1,15 +1,11 @@
 """Host bookkeeping of scrubvae_amd.data.recording (window starts, the per-rank epoch order) and the declarations of its two
 C entry points.  Nothing here needs a GPU."""
-import os
-import re
-
 import numpy as np
 import pytest
 import torch
 
+from tests import abi_header as ABI
 from tests import preprocess_checks as PC
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -95,13 +91,8 @@ def test_loader_length_needs_no_gpu(R):
 
 
 def test_entry_points_declared_and_bound():
-    from scrubvae_amd import _lib
     from scrubvae_amd import get
-    header = open(os.path.join(ROOT, "include", "scrubvae_hip.h")).read()
-    assert "Training batches from a resident recording" in header
-    declared = set(re.findall(r"\b(svae_[a-z0-9_]+)\s*\(", header))
-    for name, n_args in (("svae_window_batch", 16), ("svae_window_speed_parts", 13)):
-        assert name in declared and name in _lib.SIGNATURES
-        assert len(_lib.SIGNATURES[name][1]) == n_args
-        assert hasattr(_lib.lib(), name)
+    with open(ABI.HEADER) as f:
+        assert "Training batches from a resident recording" in f.read()
+    assert ABI.declared("svae_window_") == {"svae_window_batch", "svae_window_speed_parts"}
     assert callable(get.device_data)

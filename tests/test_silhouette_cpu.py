@@ -115,8 +115,6 @@ def test_new_exports_have_signatures():
     from scrubvae_amd import _lib
     from scrubvae_amd.eval import silhouette as SM
     lib = _lib.lib()
-    for name in ("svae_silhouette_work", "svae_silhouette", "svae_silhouette_mean", "svae_silhouette_medoids"):
-        assert name in _lib.SIGNATURES and hasattr(lib, name)
     work = lib.svae_silhouette_work
     assert work(2, 2, 2) == 0 and work(1, 0, 2) == 0            # n < 3
     assert work(10, 10, 1) == 0 and work(10, 10, 0) == 0        # K < 2
@@ -133,18 +131,6 @@ def test_new_exports_have_signatures():
     import scrubvae_amd.eval as E
     for name in ("silhouette_samples", "silhouette_score", "cluster_silhouette", "cluster_medoids"):
         assert callable(getattr(E, name))
-    assert SM.SIL_MAX_CLUSTERS == _lib.SIL_MAX_CLUSTERS == 4096
+    assert _lib.SIL_MAX_CLUSTERS == 4096
     assert SM._SIL_CALLS.keys() >= {"silhouette", "mean", "medoids"} and SM._SIL_ROWS_PER_LAUNCH % 64 == 0
     assert SM.SilhouetteParts._fields == ("s", "a", "b", "nearest")
-
-
-def test_constants_equal_the_headers():
-    import os
-    import re
-    from scrubvae_amd import _lib
-    header = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(_lib.__file__))), "include", "scrubvae_hip.h")
-    with open(header) as f:
-        text = f.read()
-    assert int(re.search(r"#define SVAE_SIL_MAX_CLUSTERS (\d+)", text).group(1)) == _lib.SIL_MAX_CLUSTERS
-    for name in ("svae_silhouette_work", "svae_silhouette", "svae_silhouette_mean", "svae_silhouette_medoids"):
-        assert re.search(rf"\b{name}\(", text)

@@ -222,10 +222,6 @@ def test_neighbour_argument_errors_before_device_work(ref, lab, q, k, kw):
 def test_new_exports_have_signatures():
     from scrubvae_amd import _lib
     lib = _lib.lib()
-    counts = dict(svae_knn_cross_work=3, svae_knn_cross=12, svae_tsne_cross_repulsion_work=3, svae_tsne_cross_repulsion=9,
-                  svae_tsne_place_step=17)
-    for name, count in counts.items():
-        assert name in _lib.SIGNATURES and hasattr(lib, name) and len(_lib.SIGNATURES[name][1]) == count
     K = _lib.KNN_MAX_K
     work = lib.svae_knn_cross_work
     assert work(0, 10, 1) == 0 and work(10, 0, 1) == 0 and work(10, 10, 0) == 0 and work(10, 10, 11) == 0 and work(10, 1000, K + 1) == 0
