@@ -58,8 +58,9 @@ import torch
 from .. import _lib, ops
 from .._lib import check
 from . import _device
-from .independence import _hsic_variable, _to_device
-from .metrics import _mmd_count, _mmd_permutation_array, _mmd_rows, mmd_permutations
+from ._device import _on_device
+from ._inputs import _feature_rows, _is_int, _variable
+from ._permutation import _count, _given_or_count, _pvalue, mmd_permutations
 from .mutual_info import _MI_CALLS, MIPermutationResult, _mi_check, _mi_neighbors, _MiRun, mi_class_terms, mi_close_labels, psi_int
 
 CMI_MAX_C, CMI_MAX_DONORS = _lib.CMI_MAX_C, _lib.CMI_MAX_DONORS   # the caps on the width of a real c and on n_donors
@@ -86,7 +87,7 @@ def cmi_class_term(count):
 
 
 def _cmi_condition(c):
-    kind, w = _hsic_variable(c)
+    kind, w = _variable(c)
     if kind == "real" and w.shape[1] > CMI_MAX_C:
         raise ValueError(f"real c must be [n] or [n, p] with 1 <= p <= {CMI_MAX_C}, got p = {w.shape[1]}")
     return kind, w
@@ -97,10 +98,8 @@ def _cmi_check(z, y, c, n_neighbors):
     them), n, k, kept (all True).  kind "strat": x, v, lab (int32 [n] in 0..K-1 over the kept rows), count [K], n (kept rows), k,
     kept (bool over the given rows).  kind "chain": joint, marginal (the checked arguments of the two label estimates), w, n, k,
     kept."""
-    x = _mmd_rows(z, "z")
-    if x.shape[1] < 1:
-        raise ValueError("z must have at least one feature")
-    ykind, v = _hsic_variable(y)
+    x = _feature_rows(z, "z")
+    ykind, v = _variable(y)
     ckind, w = _cmi_condition(c)
     rows = x.shape[0]
     if v.shape[0] != rows or w.shape[0] != rows:
@@ -112,7 +111,7 @@ def _cmi_check(z, y, c, n_neighbors):
             raise ValueError("labels for both y and c are not supported: give one of them as a real variable")
         if torch.is_tensor(x) or torch.is_tensor(w):   # the rows [z, c] where z is (where c is, for a host z)
             home = x.device if torch.is_tensor(x) else w.device
-            xc = torch.cat([_to_device(x, home), _to_device(w, home)], dim=1)
+            xc = torch.cat([_on_device(x, home), _on_device(w, home)], dim=1)
         else:
             xc = np.concatenate([x, w], axis=1)
         joint, marginal = _mi_check(xc, y, n_neighbors), _mi_check(w, y, n_neighbors)
@@ -131,17 +130,8 @@ def _cmi_check(z, y, c, n_neighbors):
     return dict(kind="strat", x=x, v=v, lab=np.ascontiguousarray(lab.reshape(-1), dtype=np.int32), count=count, n=n, k=k, kept=kept)
 
 
-def _cmi_pick(c):
-    """the array that decides the device"""
-    for key in ("x", "v", "w"):
-        a = c.get(key)
-        if torch.is_tensor(a) and a.is_cuda:
-            return a
-    return None
-
-
 def _kept_rows(a, kept, dev):
-    t = _to_device(a, dev)
+    t = _on_device(a, dev)
     return t if kept.all() else t[torch.from_numpy(kept).to(dev)].contiguous()
 
 
@@ -159,7 +149,7 @@ class _CmiRun:
         self.real = c["kind"] == "real"
         new = functools.partial(torch.empty, n, dtype=torch.int32, device=dev)
         if self.real:
-            self.C, self.clab, self.nc = _to_device(c["w"], dev), None, new()
+            self.C, self.clab, self.nc = _on_device(c["w"], dev), None, new()
             self.p = self.C.shape[1]
         else:
             self.C, self.clab, self.nc, self.p = None, torch.from_numpy(c["lab"]).to(dev), None, 1
@@ -293,7 +283,7 @@ def conditional_mutual_information(z, y, c, *, n_neighbors=3, return_parts=False
     return_parts=True: (I, dict) with those parts and kept, the bool mask over the given rows that entered the estimate.  See the
     module docstring for the definitions."""
     c_ = _cmi_check(z, y, c, n_neighbors)
-    dev = _device_of(_cmi_pick(c_))
+    dev = _device_of(c_.get("x"), c_.get("v"), c_.get("w"))
     with torch.cuda.device(dev):
         run = _cmi_run(c_, dev)
         out = torch.zeros(run.SUMS, dtype=torch.float64, device=dev)
@@ -303,7 +293,7 @@ def conditional_mutual_information(z, y, c, *, n_neighbors=3, return_parts=False
 
 
 def _donor_count(n_donors, n):
-    if isinstance(n_donors, bool) or not isinstance(n_donors, (int, np.integer)):
+    if not _is_int(n_donors):
         raise ValueError(f"n_donors must be an integer, got {n_donors!r}")
     if not 2 <= n_donors <= min(n, CMI_MAX_DONORS):
         raise ValueError(f"n_donors must lie in [2, min(n, {CMI_MAX_DONORS})] with n = {n} rows, got {n_donors}")
@@ -349,7 +339,7 @@ def _local_inputs(n, kp, P, seed, dev):
 
 
 def _conditional_permutations(kind, w, P, n_donors, seed, dev):
-    """kind, w: c as _hsic_variable gives it (the kept rows); checked arguments"""
+    """kind, w: c as _variable gives it (the kept rows); checked arguments"""
     with torch.cuda.device(dev):
         if kind == "labels":
             lab = (torch.from_numpy(w) if not torch.is_tensor(w) else w).to(dev)
@@ -363,7 +353,7 @@ def _conditional_permutations(kind, w, P, n_donors, seed, dev):
             out = torch.empty_like(shuffled)
             out.scatter_(1, sorted_.view(1, -1).expand(P, -1), shuffled)
             return out
-        C = _to_device(w, dev)
+        C = _on_device(w, dev)
         n = C.shape[0]
         nbr = _local_donors(C, n_donors)
         order, scan_of = _local_inputs(n, n_donors, P, seed, dev)
@@ -388,16 +378,15 @@ def conditional_permutations(c, n_permutations, *, n_donors=8, seed=0, device=No
     exceeds 2^19 so that the scan orders of one launch stay under 2^25 entries (_local_chunk).
     2 <= n_donors <= min(n, CMI_MAX_DONORS) and n <= 2^19 for a real c (ValueError otherwise); n_donors is not read for labels."""
     kind, w = _cmi_condition(c)
-    P = _mmd_count(n_permutations)
+    P = _count(n_permutations)
     if kind == "real":
         _donor_count(n_donors, w.shape[0])
-    dev = torch.device(device) if device is not None else _device_of(w if torch.is_tensor(w) and w.is_cuda else None)
+    dev = torch.device(device) if device is not None else _device_of(w)
     return _conditional_permutations(kind, w, P, n_donors, seed, dev)
 
 
-def _cmi_given_permutations(permutations, n):
-    """the errors of a given `permutations`, where it lives -> an integer torch tensor [P, n] with entries in [0, n)"""
-    t = _mmd_permutation_array(permutations, n)
+def _cmi_given_permutations(t, n):
+    """the further error of a given `permutations` that passed _given_or_count, where it lives: an entry outside [0, n)"""
     if int(t.min()) < 0 or int(t.max()) >= n:
         raise ValueError(f"permutations must hold row indices in [0, {n})")
     return t
@@ -423,15 +412,12 @@ def conditional_mutual_information_permutation_test(z, y, c, *, n_neighbors=3, n
     per 64 permutations."""
     c_ = _cmi_check(z, y, c, n_neighbors)
     n = c_["n"]
-    perms = None
-    if permutations is None:
-        P = _mmd_count(n_permutations)
-        if c_["kind"] != "strat":
-            _donor_count(n_donors, n)
-    else:
-        perms = _cmi_given_permutations(permutations, n)
-        P = perms.shape[0]
-    dev = _device_of(_cmi_pick(c_))
+    perms, P = _given_or_count(permutations, n_permutations, n)
+    if perms is not None:
+        _cmi_given_permutations(perms, n)
+    elif c_["kind"] != "strat":
+        _donor_count(n_donors, n)
+    dev = _device_of(c_.get("x"), c_.get("v"), c_.get("w"))
     with torch.cuda.device(dev):
         if perms is not None:
             perms = perms.to(device=dev, dtype=torch.int64)
@@ -450,5 +436,4 @@ def conditional_mutual_information_permutation_test(z, y, c, *, n_neighbors=3, n
             for p in range(count):
                 run.run(out[p], perms[p0 + p])
             null[p0: p0 + count] = run.close(out[:count].cpu().numpy())
-    pvalue = (1 + int((null >= statistic).sum())) / (1 + P)
-    return MIPermutationResult(statistic, pvalue, null)
+    return MIPermutationResult(statistic, _pvalue(statistic, null), null)

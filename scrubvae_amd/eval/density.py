@@ -61,8 +61,8 @@ import torch
 from .. import _lib, ops
 from .._lib import check
 from . import _device
-from .independence import _to_device
-from .metrics import _mmd_rows
+from ._device import _on_device
+from ._inputs import _finite_rows, _is_int
 
 DENSITY_MAX_GRID = _lib.DENSITY_MAX_GRID  # the cap on each side of the grid
 _DENSITY_CALLS = {"grid": 0}              # launches of svae_density_grid by this process
@@ -75,11 +75,12 @@ _device_of = functools.partial(_device._device_of, who="the density map runs on 
 
 # ---- argument checks, before any device work ------------------------------------------------------------------------------------
 def _is_number(v):
+    """a number, finite or not: the range checks below refuse inf and nan in their own words"""
     return not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating))
 
 
 def _den_rows(y):
-    x = _mmd_rows(y, "y")
+    x = _finite_rows(y, "y")
     if x.shape[1] != 2 or x.shape[0] < 1:
         raise ValueError(f"y must be [n >= 1, 2], got shape {tuple(x.shape)}")
     if x.shape[0] > 2 ** 30:
@@ -89,7 +90,7 @@ def _den_rows(y):
 
 def _den_grid_size(grid_size):
     g = (grid_size, grid_size) if _is_number(grid_size) else tuple(grid_size) if isinstance(grid_size, (tuple, list)) else None
-    if g is None or len(g) != 2 or not all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in g):
+    if g is None or len(g) != 2 or not all(_is_int(v) for v in g):
         raise ValueError(f"grid_size must be an int or (gx, gy), got {grid_size!r}")
     gx, gy = int(g[0]), int(g[1])
     if not (2 <= gx <= DENSITY_MAX_GRID and 2 <= gy <= DENSITY_MAX_GRID):
@@ -113,7 +114,7 @@ def _den_bandwidth(bandwidth, n_neighbors, x):
         if bandwidth not in ("scott", "knn"):
             raise ValueError(f'bandwidth must be a positive number, an [n] array, "scott" or "knn", got {bandwidth!r}')
         if bandwidth == "knn":
-            if isinstance(n_neighbors, bool) or not isinstance(n_neighbors, (int, np.integer)):
+            if not _is_int(n_neighbors):
                 raise ValueError(f'bandwidth="knn" needs an integer n_neighbors, got {n_neighbors!r}')
             from .neighbors import KNN_MAX_K
             if not 1 <= n_neighbors <= min(n - 1, KNN_MAX_K):
@@ -175,11 +176,11 @@ def _density_device(x, h, h_rows, x0, dx, gx, y0, dy, gy, info=None):
     dev = _device_of(x)
     with torch.cuda.device(dev):
         lib = _lib.lib()
-        Y = x.to(dev) if torch.is_tensor(x) else _to_device(x, dev)
+        Y = x.to(dev) if torch.is_tensor(x) else _on_device(x, dev)
         if Y.stride(1) != 1 or Y.stride(0) < 2:
             Y = Y.contiguous()
         n = Y.shape[0]
-        hr = None if h_rows is None else _to_device(h_rows, dev)
+        hr = None if h_rows is None else _on_device(h_rows, dev)
         nbytes = lib.svae_density_work(n, gx, gy)
         if nbytes <= 0:
             raise ValueError(f"density: sizes out of range (n={n} grid {gx} x {gy})")

@@ -34,6 +34,7 @@ last update); results are bit-reproducible.  ValueError, before any device work,
 non-finite rows."""
 from __future__ import annotations
 
+import functools
 import math
 
 import numpy as np
@@ -41,8 +42,9 @@ import torch
 
 from .. import _lib, ops
 from .._lib import check
-from ._device import _clock
-from .metrics import _device_of, _mmd_rows
+from . import _device
+from ._device import _clock, _on_device
+from ._inputs import _feature_rows, _is_int, _is_number
 from .neighbors import KNN_MAX_K, _knn_device
 
 _EXPLORATION_ITER = 250      # iterations with early exaggeration (sklearn's _EXPLORATION_MAX_ITER)
@@ -50,10 +52,12 @@ _N_ITER_CHECK = 50           # iterations between two looks at the KL value and 
 _TSNE_CALLS = {"search": 0, "repulsion": 0, "step": 0, "sums": 0, "host_reads": 0}  # launches / device-to-host reads by this process
 _TSNE_LAST = {"work": 0, "chunks": 0, "kl_checks": []}  # doubles of repulsion work, column chunks, (iteration, KL) of the last fit
 
+_device_of = functools.partial(_device._device_of, who="t-SNE runs on the GPU (csrc/tsne.hip); no device is available")
+
 
 def _tsne_neighbors(n, perplexity):
     """the argument errors of the perplexity -> k"""
-    if isinstance(perplexity, bool) or not isinstance(perplexity, (int, float, np.integer, np.floating)) or not math.isfinite(perplexity):
+    if not _is_number(perplexity):
         raise ValueError(f"perplexity must be a finite number, got {perplexity!r}")
     if perplexity <= 0:
         raise ValueError(f"perplexity must be positive, got {perplexity}")
@@ -69,10 +73,8 @@ def _tsne_neighbors(n, perplexity):
 
 
 def _tsne_rows(z):
-    x = _mmd_rows(z, "z")
-    n, d = x.shape
-    if d < 1:
-        raise ValueError("z must have at least one feature")
+    x = _feature_rows(z, "z")
+    n = x.shape[0]
     if n < 2:
         raise ValueError(f"t-SNE needs at least 2 rows, got {n}")
     if n > 2 ** 26:
@@ -271,13 +273,12 @@ class TSNE:
         x = _tsne_rows(z)
         n, d = x.shape
         k = _tsne_neighbors(n, self.perplexity)
-        if isinstance(self.max_iter, bool) or not isinstance(self.max_iter, (int, np.integer)) or self.max_iter < _EXPLORATION_ITER:
+        if not _is_int(self.max_iter) or self.max_iter < _EXPLORATION_ITER:
             raise ValueError(f"max_iter must be an integer >= {_EXPLORATION_ITER}, got {self.max_iter!r}")
         if not isinstance(self.early_exaggeration, (int, float, np.integer, np.floating)) or not self.early_exaggeration >= 1 \
                 or not math.isfinite(self.early_exaggeration):
             raise ValueError(f"early_exaggeration must be at least 1, got {self.early_exaggeration!r}")
-        if isinstance(self.n_iter_without_progress, bool) or not isinstance(self.n_iter_without_progress, (int, np.integer)) \
-                or self.n_iter_without_progress < -1:
+        if not _is_int(self.n_iter_without_progress) or self.n_iter_without_progress < -1:
             raise ValueError(f"n_iter_without_progress must be an integer >= -1, got {self.n_iter_without_progress!r}")
         if not isinstance(self.min_grad_norm, (int, float, np.integer, np.floating)) or not self.min_grad_norm >= 0:
             raise ValueError(f"min_grad_norm must be a number >= 0, got {self.min_grad_norm!r}")
@@ -286,8 +287,7 @@ class TSNE:
                 raise ValueError(f'learning_rate must be "auto" or a positive number, got {self.learning_rate!r}')
             lr = _auto_learning_rate(n, self.early_exaggeration)
         else:
-            if isinstance(self.learning_rate, bool) or not isinstance(self.learning_rate, (int, float, np.integer, np.floating)) \
-                    or not (math.isfinite(self.learning_rate) and self.learning_rate > 0):
+            if not _is_number(self.learning_rate) or not self.learning_rate > 0:
                 raise ValueError(f'learning_rate must be "auto" or a positive number, got {self.learning_rate!r}')
             lr = float(self.learning_rate)
         if isinstance(self.init, str):
@@ -315,9 +315,7 @@ class TSNE:
         x, k, init, lr = self._check(z)
         dev = _device_of(x)
         with torch.cuda.device(dev):
-            if not torch.is_tensor(x):
-                x = torch.from_numpy(x if x.flags.writeable else x.copy())
-            x = x.to(dev).contiguous()
+            x = _on_device(x, dev)
             rowptr, col, val, _ = _affinities_device(x, k, self.perplexity, info)
             Y = (_pca_init(x) if isinstance(init, str) else torch.from_numpy(init).to(dev)).contiguous()
             phases = _tsne_schedule(self.max_iter, self.n_iter_without_progress, self.early_exaggeration)

@@ -40,8 +40,8 @@ import torch
 from .. import _lib, ops
 from .._lib import check
 from . import _device
-from .independence import _to_device
-from .metrics import _mmd_rows
+from ._device import _on_device
+from ._inputs import _feature_rows, _is_int
 from .neighbors import KNN_MAX_K, _knn_device
 
 _RANK_CALLS = {"ranks": 0, "curves": 0}   # launches of the entry points by this process
@@ -115,9 +115,7 @@ class EmbeddingQuality:
 
 # ---- argument checks, before any device work ------------------------------------------------------------------------------------
 def _eq_rows(a, name):
-    x = _mmd_rows(a, name)
-    if x.shape[1] < 1:
-        raise ValueError(f"{name} must have at least one feature")
+    x = _feature_rows(a, name)
     if x.shape[0] >= 2 ** 31:
         raise ValueError(f"at most 2^31 - 1 rows are supported, got {x.shape[0]}")
     return x
@@ -131,7 +129,7 @@ def _eq_pair(X, X_embedded):
 
 
 def _eq_count(value, n, name, half):
-    if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
+    if not _is_int(value):
         raise ValueError(f"{name} must be an integer, got {value!r}")
     k = int(value)
     if k < 1:
@@ -207,14 +205,14 @@ def neighbor_ranks(x, idx):
     table = _eq_idx(idx, z.shape[0])
     dev = _device_of(z)
     with torch.cuda.device(dev):
-        return _ranks_device(_to_device(z, dev), torch.from_numpy(table).to(dev)).cpu().numpy()
+        return _ranks_device(_on_device(z, dev), torch.from_numpy(table).to(dev)).cpu().numpy()
 
 
 def _one_sided(inside, seen, k):
     """the penalty sum at k of the k neighbours in `seen`, ranked in `inside`"""
-    dev = _device_of(inside if torch.is_tensor(inside) and inside.is_cuda else seen)
+    dev = _device_of(inside, seen)
     with torch.cuda.device(dev):
-        rank = _cross_ranks(_to_device(inside, dev), _to_device(seen, dev), k)
+        rank = _cross_ranks(_on_device(inside, dev), _on_device(seen, dev), k)
         pen, _, _ = _curves_device(rank)
     return int(pen[k - 1])
 
@@ -247,9 +245,9 @@ def embedding_quality(X, X_embedded, *, max_neighbors=30, rows_at=None):
         at = _eq_count(rows_at, n, "rows_at", half=False)
         if at > K:
             raise ValueError(f"rows_at must be at most max_neighbors = {K}, got {at}")
-    dev = _device_of(x if torch.is_tensor(x) and x.is_cuda else y)
+    dev = _device_of(x, y)
     with torch.cuda.device(dev):
-        Zx, Zy = _to_device(x, dev), _to_device(y, dev)
+        Zx, Zy = _on_device(x, dev), _on_device(y, dev)
         pen_t, hit, rows_t = _curves_device(_cross_ranks(Zx, Zy, K), at)
         pen_c, _, rows_c = _curves_device(_cross_ranks(Zy, Zx, K), at)
     return EmbeddingQuality(n, pen_t, pen_c, hit, rows_at=at or None, intrusion_rows=rows_t, extrusion_rows=rows_c)

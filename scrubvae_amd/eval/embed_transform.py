@@ -30,6 +30,7 @@ every launch is a plain launch on the current stream.  ValueError, before any de
 non-finite rows."""
 from __future__ import annotations
 
+import functools
 import math
 
 import numpy as np
@@ -37,10 +38,11 @@ import torch
 
 from .. import _lib, ops
 from .._lib import check
-from ._device import _clock
+from . import _device
+from ._device import _clock, _on_device
+from ._inputs import _feature_rows, _finite_rows, _is_int, _is_number
 from .embed import _search_device, _tsne_neighbors
-from .metrics import _device_of, _mmd_rows
-from .neighbors import _knn_cross_device, _rows_on
+from .neighbors import _knn_cross_device
 
 _MAX_ROWS = 2 ** 26          # rows of the map, and rows of a batch (svae_tsne_cross_repulsion)
 # launches and device-to-host reads by this process
@@ -49,15 +51,17 @@ _PLACE_CALLS = {"knn": 0, "search": 0, "repulsion": 0, "step": 0, "host_reads": 
 # (launches of its batch made before it, launches of the whole batch)
 _PLACE_LAST = {"work": 0, "chunks": 0, "batches": 0, "reads_at": []}
 
+_device_of = functools.partial(_device._device_of, who="the t-SNE map runs on the GPU (csrc/tsne.hip); no device is available")
+
 
 def _number(v, name, ok, want):
-    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v) or not ok(v):
+    if not _is_number(v) or not ok(v):
         raise ValueError(f"{name} must be {want}, got {v!r}")
     return float(v)
 
 
 def _integer(v, name, least):
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < least:
+    if not _is_int(v) or v < least:
         raise ValueError(f"{name} must be an integer >= {least}, got {v!r}")
     return int(v)
 
@@ -116,10 +120,8 @@ class TSNEMap:
     first transform and stay there."""
 
     def __init__(self, z_ref, embedding, *, perplexity=30.0):
-        x = _mmd_rows(z_ref, "z_ref")
-        n, d = x.shape
-        if d < 1:
-            raise ValueError("z_ref must have at least one feature")
+        x = _feature_rows(z_ref, "z_ref")
+        n = x.shape[0]
         if n < 1:
             raise ValueError("z_ref must have at least one row")
         if n > _MAX_ROWS:
@@ -139,7 +141,7 @@ class TSNEMap:
         return cls(z, tsne.embedding_, perplexity=tsne.perplexity)
 
     def _check(self, z_new, max_iter, learning_rate, momentum, exaggeration, max_grad_norm, init, batch_rows):
-        q = _mmd_rows(z_new, "z_new")
+        q = _finite_rows(z_new, "z_new")
         m = q.shape[0]
         if q.shape[1] != self._x.shape[1]:
             raise ValueError(f"z_new has {q.shape[1]} features, the map's rows have {self._x.shape[1]}")
@@ -161,9 +163,9 @@ class TSNEMap:
     def _device(self, q):
         """(X [n, d], Yref [n, 2]) on the device of the first transform's rows (or the current one)"""
         if self._dev is None:
-            dev = _device_of(q) if torch.is_tensor(q) and q.is_cuda else _device_of(self._x)
+            dev = _device_of(q, self._x)
             with torch.cuda.device(dev):
-                self._dev = (_rows_on(self._x, dev), torch.from_numpy(self._y).to(dev).contiguous())
+                self._dev = (_on_device(self._x, dev), torch.from_numpy(self._y).to(dev).contiguous())
         return self._dev
 
     def transform(self, z_new, *, max_iter=250, learning_rate=0.1, momentum=0.8, exaggeration=1.0, max_grad_norm=0.25, init="weighted",
@@ -181,7 +183,7 @@ class TSNEMap:
             for b0 in range(0, m, batch_rows):
                 b1 = min(m, b0 + batch_rows)
                 rows = b1 - b0
-                Q = _rows_on(q[b0:b1], dev)
+                Q = _on_device(q[b0:b1], dev)
                 Y0 = None if isinstance(init, str) else torch.from_numpy(init[b0:b1]).to(dev).contiguous()
                 rep = _CrossRepulsion(rows, Yref)
                 update = torch.zeros(rows, 2, dtype=torch.float64, device=dev)

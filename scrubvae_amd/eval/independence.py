@@ -41,7 +41,6 @@ and the permutation errors of mmd_permutation_test.
 from __future__ import annotations
 
 import functools
-import math
 
 import numpy as np
 import torch
@@ -49,8 +48,9 @@ import torch
 from .. import _lib, ops
 from .._lib import check
 from . import _device
-from ._device import _clock
-from .metrics import _mmd_check_permutations, _mmd_count, _mmd_permutation_array, _mmd_rows, mmd_permutations
+from ._device import _clock, _on_device
+from ._inputs import _feature_rows, _finite_rows, _is_number, _variable
+from ._permutation import _given_or_count, _on_device_or_drawn, _pvalue
 
 HSIC_MAX_Y = _lib.HSIC_MAX_Y      # the widest real y
 HSIC_ESTIMATORS = {"biased": 2, "unbiased": 4}  # estimator -> the smallest n
@@ -76,47 +76,16 @@ class HSICPermutationResult:
 
 
 def _hsic_bandwidth_arg(h, name):
-    if h is not None:
-        if isinstance(h, bool) or not isinstance(h, (int, float, np.integer, np.floating)) or not (math.isfinite(h) and h > 0):
-            raise ValueError(f"{name} must be a finite positive number, got {h!r}")
-
-
-def _hsic_variable(y):
-    """y -> ("real", fp64 rows [n, q] where they are) or ("labels", int32 numpy [n] in 0..K-1 on the host)"""
-    if torch.is_tensor(y):
-        t = y.detach()
-        integer = not (t.is_floating_point() or t.is_complex() or t.dtype == torch.bool)
-        floating = t.is_floating_point()
-        ndim = t.dim()
-    else:
-        t = np.asarray(y)
-        integer, floating, ndim = t.dtype.kind in "iu", t.dtype.kind == "f", t.ndim
-    if integer:
-        if ndim != 1:
-            raise ValueError(f"integer y holds labels and must be 1-D, got {ndim}-D")
-        lab = t.cpu().numpy() if torch.is_tensor(t) else t
-        uniq, inv = np.unique(lab, return_inverse=True)
-        if len(uniq) < 2:
-            raise ValueError("labels y need at least two distinct values")
-        return "labels", np.ascontiguousarray(inv.reshape(-1), dtype=np.int32)
-    if not floating:
-        raise ValueError(f"y must be of a floating or an integer dtype, got {t.dtype}")
-    if ndim == 1:
-        t = t.reshape(-1, 1)
-    rows = _mmd_rows(t, "y")
-    if not 1 <= rows.shape[1] <= HSIC_MAX_Y:
-        raise ValueError(f"real y must be [n] or [n, q] with 1 <= q <= {HSIC_MAX_Y}, got q = {rows.shape[1]}")
-    return "real", rows
+    if h is not None and (not _is_number(h) or not h > 0):
+        raise ValueError(f"{name} must be a finite positive number, got {h!r}")
 
 
 def _hsic_check(z, y, hz, hy, estimator):
-    """the argument errors of hsic*, before any device work -> (fp64 rows of z, kind, y as _hsic_variable gives it)"""
+    """the argument errors of hsic*, before any device work -> (fp64 rows of z, kind, y as _variable gives it)"""
     if estimator not in HSIC_ESTIMATORS:
         raise ValueError(f"estimator must be one of {sorted(HSIC_ESTIMATORS)}, got {estimator!r}")
-    x = _mmd_rows(z, "z")
-    if x.shape[1] < 1:
-        raise ValueError("z must have at least one feature")
-    kind, v = _hsic_variable(y)
+    x = _feature_rows(z, "z")
+    kind, v = _variable(y)
     n = x.shape[0]
     if v.shape[0] != n:
         raise ValueError(f"z and y must have one row count, got {n} and {v.shape[0]}")
@@ -127,12 +96,6 @@ def _hsic_check(z, y, hz, hy, estimator):
     if kind == "labels" and hy is not None:
         raise ValueError("hy belongs to a real y: the delta kernel on labels has no bandwidth")
     return x, kind, v
-
-
-def _to_device(a, dev):
-    if not torch.is_tensor(a):
-        a = torch.from_numpy(a if a.flags.writeable else a.copy())  # torch refuses to share a read-only array
-    return a.to(dev).contiguous()
 
 
 def _hsic_select(lib, rows, h, st):
@@ -166,29 +129,24 @@ def hsic_close(A, S, C, D, n, estimator):
 
 def _hsic_run(checked, hz, hy, estimator, perms=None, n_permutations=0, seed=0, info=None):
     """Everything on the device of z (or of y, or the current one) for checked = _hsic_check(...) -> a dict: values [1 + P] (the
-    statistic, then the null), hz, hy, normalized and its parts num, den_z, den_y.  perms: an array that
-    passed _mmd_permutation_array, or None to draw n_permutations (0: none) by mmd_permutations.  info (a dict) receives
-    synchronised host-clock times."""
+    statistic, then the null), hz, hy, normalized and its parts num, den_z, den_y.  perms: what _given_or_count
+    returned, None to draw n_permutations (0: none) by mmd_permutations.  info (a dict) receives synchronised host-clock times."""
     x, kind, v = checked
     n, d = x.shape
     P = n_permutations if perms is None else perms.shape[0]
-    pick = x if torch.is_tensor(x) and x.is_cuda else (v if kind == "real" else None)
-    dev = _device_of(pick)
+    dev = _device_of(x, v)   # labels are a host array
     tilde = 1 if estimator == "unbiased" else 0
     with torch.cuda.device(dev):
-        if perms is not None:
-            perms = perms.to(device=dev, dtype=torch.int64)
-            _mmd_check_permutations(perms)
-        elif P:
-            perms = mmd_permutations(n, P, seed, dev)
+        if P:
+            perms = _on_device_or_drawn(perms, n, P, seed, dev)
         lib = _lib.lib()
         st = ops._stream()
-        Z = _to_device(x, dev)
+        Z = _on_device(x, dev)
         clock = functools.partial(_clock, dev, info is not None)
         t0 = clock()
         hzm = _hsic_select(lib, Z, hz, st)
         if kind == "real":
-            Y, lab, q = _to_device(v, dev), None, v.shape[1]
+            Y, lab, q = _on_device(v, dev), None, v.shape[1]
             hym = _hsic_select(lib, Y, hy, st)
             yp, lp, hyp = Y.data_ptr(), None, hym[1:].data_ptr()
         else:
@@ -246,12 +204,12 @@ def hsic_bandwidth(a):
     the rows, squared -- exact, as mmd_bandwidth is for two sets."""
     if (torch.is_tensor(a) and a.dim() == 1) or (not torch.is_tensor(a) and np.ndim(a) == 1):
         a = a.reshape(-1, 1)
-    x = _mmd_rows(a, "a")
+    x = _finite_rows(a, "a")
     if x.shape[0] < 2 or x.shape[1] < 1:
         raise ValueError(f"the bandwidth needs at least 2 rows of at least 1 feature, got shape {tuple(x.shape)}")
     dev = _device_of(x)
     with torch.cuda.device(dev):
-        return float(_hsic_select(_lib.lib(), _to_device(x, dev), None, ops._stream()).cpu()[1])
+        return float(_hsic_select(_lib.lib(), _on_device(x, dev), None, ops._stream()).cpu()[1])
 
 
 def hsic(z, y, *, hz=None, hy=None, estimator="biased"):
@@ -274,13 +232,7 @@ def hsic_permutation_test(z, y, *, hz=None, hy=None, estimator="biased", n_permu
     None, P = n_permutations rows are drawn by mmd_permutations(n, n_permutations, seed, device): the result equals the call with
     those permutations bit for bit.  1 <= P <= MMD_MAX_PERMUTATIONS = 65 536."""
     checked = _hsic_check(z, y, hz, hy, estimator)
-    perms = None
-    if permutations is None:
-        P = _mmd_count(n_permutations)
-    else:
-        perms = _mmd_permutation_array(permutations, checked[0].shape[0])
-        P = perms.shape[0]
+    perms, P = _given_or_count(permutations, n_permutations, checked[0].shape[0])
     r = _hsic_run(checked, hz, hy, estimator, perms, P, seed)
     statistic, null = float(r["values"][0]), np.ascontiguousarray(r["values"][1:])
-    pvalue = float("nan") if math.isnan(statistic) else (1 + int((null >= statistic).sum())) / (1 + P)
-    return HSICPermutationResult(statistic, pvalue, null, r["hz"], r["hy"], r["normalized"])
+    return HSICPermutationResult(statistic, _pvalue(statistic, null), null, r["hz"], r["hy"], r["normalized"])

@@ -62,7 +62,6 @@ Differences from the reference, by design:
 from __future__ import annotations
 
 import functools
-import math
 import warnings
 
 import numpy as np
@@ -72,6 +71,9 @@ from .. import _lib, ops
 from .._lib import check
 from . import _device
 from ._device import _clock
+from ._inputs import _finite_rows, _is_number
+from ._permutation import MMD_MAX_PERMUTATIONS, _given_or_count, _on_device_or_drawn, _pvalue, mmd_permutations  # noqa: F401
+from .neighbors import _knn_check, _knn_device
 
 _RTOL_PIVOT = 1e-12   # svae_spd_factor_solve_f64: pivots <= this x max diagonal are zero directions
 LOGREG_C, LOGREG_L1_RATIO = 1.0, 0.5
@@ -369,7 +371,6 @@ def lda_rand_cv(z, y_true, window=51, folds=5):
 
 def _knn_cv_check(z, window, folds, n_neighbors):
     """the argument errors of the kNN probes -> (the rows z[0::window] in fp64, their folds, k, the folds as int32 groups)"""
-    from .neighbors import _knn_check
     t = (z if torch.is_tensor(z) else np.asarray(z))[0::window]
     if t.ndim != 2:
         t = t.reshape(t.shape[0], -1)
@@ -380,7 +381,6 @@ def _knn_cv_check(z, window, folds, n_neighbors):
 
 def _knn_cv_search(x, k, grp):
     """each row's k nearest rows of the other folds, int64 [n, k] on the device: ONE neighbour search with group = fold"""
-    from .neighbors import _knn_device
     return _knn_device(x, k, grp)[1].long()
 
 
@@ -742,36 +742,16 @@ def hungarian_match(x1, x2):
 _MMD_CALLS = {"select": 0, "sums": 0, "null": 0}  # launches of svae_mmd_select / svae_mmd_sums / svae_mmd_null by this process
 
 
-def _mmd_rows(A, name):
-    """[n, d] -> fp64 rows where they are (torch tensor or numpy), checked finite"""
-    if torch.is_tensor(A):
-        t = A.detach()
-        if t.dim() != 2:
-            raise ValueError(f"{name}: expected a 2-D array of rows, got {t.dim()}-D")
-        t = t.to(torch.float64)
-        finite = bool(torch.isfinite(t).all()) if t.numel() else True
-    else:
-        t = np.asarray(A)
-        if t.ndim != 2:
-            raise ValueError(f"{name}: expected a 2-D array of rows, got {t.ndim}-D")
-        t = np.ascontiguousarray(t, dtype=np.float64)
-        finite = bool(np.isfinite(t).all())
-    if not finite:
-        raise ValueError(f"{name} holds non-finite values")
-    return t
-
-
 def _mmd_check(X, Y, h):
     """the argument errors of mmd_*, before any device work -> the fp64 rows (x, y)"""
-    x, y = _mmd_rows(X, "X"), _mmd_rows(Y, "Y")
+    x, y = _finite_rows(X, "X"), _finite_rows(Y, "Y")
     nx, ny = x.shape[0], y.shape[0]
     if nx < 2 or ny < 2:
         raise ValueError(f"the MMD estimate needs at least 2 rows on each side, got {nx} and {ny}")
     if x.shape[1] != y.shape[1] or x.shape[1] < 1:
         raise ValueError(f"X and Y must share one feature count >= 1, got {x.shape[1]} and {y.shape[1]}")
-    if h is not None:
-        if isinstance(h, bool) or not isinstance(h, (int, float, np.integer, np.floating)) or not (math.isfinite(h) and h > 0):
-            raise ValueError(f"h must be a finite positive number, got {h!r}")
+    if h is not None and (not _is_number(h) or not h > 0):
+        raise ValueError(f"h must be a finite positive number, got {h!r}")
     return x, y
 
 
@@ -782,7 +762,7 @@ def _mmd_device(X, Y, h, want_h, info=None, keep=None):
     x, y = _mmd_check(X, Y, h)
     nx, ny = x.shape[0], y.shape[0]
     n, d = nx + ny, x.shape[1]
-    dev = _device_of(x if torch.is_tensor(x) and x.is_cuda else y)
+    dev = _device_of(x, y)
     with torch.cuda.device(dev):
         lib = _lib.lib()
         blocks = lib.svae_mmd_blocks(n)
@@ -825,7 +805,6 @@ def mmd_estimate(X, Y, h=None):
     return float(_mmd_device(X, Y, h, False)[1][3])
 
 
-MMD_MAX_PERMUTATIONS = _lib.MMD_NULL_MAX  # the cap on n_permutations: 65 536 (2.4e-5 resolves a p-value of 1.5e-5)
 _MMD_NULL_LAUNCH = 1024                   # permutations per svae_mmd_null launch: bounds the partials and the label scratch
 
 
@@ -839,51 +818,6 @@ class MMDPermutationResult:
     def __repr__(self):
         return (f"MMDPermutationResult(statistic={self.statistic!r}, pvalue={self.pvalue!r}, "
                 f"null_distribution=<{len(self.null_distribution)} values>, h={self.h!r})")
-
-
-def mmd_permutations(n, n_permutations, seed, device):
-    """[n_permutations, n] int64 on `device`, every row a uniformly drawn permutation of range(n): the argsort of uniform keys from
-    a torch.Generator on that device seeded with `seed`.  Reproducible for a given seed, torch build and device type."""
-    n, P = int(n), int(n_permutations)
-    if n < 1 or P < 1:
-        raise ValueError(f"mmd_permutations needs n >= 1 and n_permutations >= 1, got {n} and {P}")
-    device = torch.device(device)
-    g = torch.Generator(device=device)
-    g.manual_seed(int(seed))
-    return torch.rand(P, n, generator=g, device=device).argsort(dim=1)
-
-
-def _mmd_count(n_permutations):
-    if isinstance(n_permutations, bool) or not isinstance(n_permutations, (int, np.integer)):
-        raise ValueError(f"n_permutations must be an integer, got {n_permutations!r}")
-    if not 1 <= n_permutations <= MMD_MAX_PERMUTATIONS:
-        raise ValueError(f"n_permutations must lie in [1, {MMD_MAX_PERMUTATIONS}], got {n_permutations}")
-    return int(n_permutations)
-
-
-def _mmd_permutation_array(permutations, n):
-    """the shape and dtype errors of a given `permutations`, on the host -> an integer torch tensor [P, n] where it is"""
-    if torch.is_tensor(permutations):
-        t = permutations.detach()
-    else:
-        a = np.asarray(permutations)
-        t = torch.as_tensor(a if a.flags.writeable else a.copy())  # torch refuses to share a read-only array
-    if t.dim() != 2 or t.shape[1] != n or t.shape[0] < 1:
-        raise ValueError(f"permutations must be [P, n = {n}] with P >= 1, got shape {tuple(t.shape)}")
-    if t.dtype not in (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8):
-        raise ValueError(f"permutations must hold integers, got {t.dtype}")
-    _mmd_count(t.shape[0])
-    return t
-
-
-def _mmd_check_permutations(perms):
-    """ValueError unless every row of perms [P, n] (a torch tensor, checked where it lives) is a permutation of range(n)"""
-    n = perms.shape[1]
-    want = torch.arange(n, device=perms.device, dtype=perms.dtype)
-    for p0 in range(0, perms.shape[0], _MMD_NULL_LAUNCH):
-        ok = (perms[p0: p0 + _MMD_NULL_LAUNCH].sort(dim=1).values == want).all(dim=1)
-        if not bool(ok.all()):
-            raise ValueError(f"permutations[{p0 + int((~ok).nonzero()[0])}] is not a permutation of range({n})")
 
 
 def _mmd_label_bits(perms, nx):
@@ -941,22 +875,12 @@ def mmd_permutation_test(X, Y, h=None, n_permutations=1000, seed=0, permutations
     1 <= P <= MMD_MAX_PERMUTATIONS = 65 536.  Inputs and argument errors otherwise as for mmd_estimate."""
     x, y = _mmd_check(X, Y, h)
     nx, n, d = x.shape[0], x.shape[0] + y.shape[0], x.shape[1]
-    perms = None
-    if permutations is None:
-        P = _mmd_count(n_permutations)
-    else:
-        perms = _mmd_permutation_array(permutations, n)
-        P = perms.shape[0]
-    dev = _device_of(x if torch.is_tensor(x) and x.is_cuda else y)
+    perms, P = _given_or_count(permutations, n_permutations, n)
+    dev = _device_of(x, y)
     with torch.cuda.device(dev):
-        if perms is None:
-            perms = mmd_permutations(n, P, seed, dev)
-        else:
-            perms = perms.to(device=dev, dtype=torch.int64)
-            _mmd_check_permutations(perms)
+        perms = _on_device_or_drawn(perms, n, P, seed, dev)
         keep = {}
         hv, out = _mmd_device(x, y, h, False, keep=keep)
         null = _mmd_null_device(keep["Z"], keep["hm"], nx, perms).cpu().numpy()
     statistic = float(out[3])
-    pvalue = float("nan") if math.isnan(statistic) else (1 + int((null >= statistic).sum())) / (1 + P)
-    return MMDPermutationResult(statistic, pvalue, null, hv)
+    return MMDPermutationResult(statistic, _pvalue(statistic, null), null, hv)

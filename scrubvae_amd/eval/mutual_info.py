@@ -54,8 +54,9 @@ import torch
 from .. import _lib, ops
 from .._lib import check
 from . import _device
-from .independence import _hsic_variable, _to_device
-from .metrics import _mmd_check_permutations, _mmd_count, _mmd_permutation_array, _mmd_rows, mmd_permutations
+from ._device import _on_device
+from ._inputs import _feature_rows, _is_int, _variable
+from ._permutation import _given_or_count, _on_device_or_drawn, _pvalue
 
 MI_MAX_K, MI_MAX_Y = _lib.MI_MAX_K, _lib.MI_MAX_Y   # the caps on n_neighbors and on the width of a real y
 _MI_READ = 64                                       # permutations per read-back of the device sums
@@ -115,7 +116,7 @@ def mi_close_labels(n, mk, mc, sum_z):
 
 
 def _mi_neighbors(n_neighbors, n):
-    if isinstance(n_neighbors, bool) or not isinstance(n_neighbors, (int, np.integer)):
+    if not _is_int(n_neighbors):
         raise ValueError(f"n_neighbors must be an integer, got {n_neighbors!r}")
     if not 1 <= n_neighbors <= min(n - 1, MI_MAX_K):
         raise ValueError(f"n_neighbors must lie in [1, min(n - 1, {MI_MAX_K})] with n = {n} rows, got {n_neighbors}")
@@ -125,10 +126,8 @@ def _mi_neighbors(n_neighbors, n):
 def _mi_check(z, y, n_neighbors):
     """the argument errors, before any device work -> a dict: x (fp64 rows of z where they are, all of them), kind, n (kept rows),
     k, kept (bool [rows of z] numpy) and v (fp64 rows [n, q] where they are) or lab (int32 [n] in 0..K-1), count [K], kk [n]"""
-    x = _mmd_rows(z, "z")
-    if x.shape[1] < 1:
-        raise ValueError("z must have at least one feature")
-    kind, v = _hsic_variable(y)
+    x = _feature_rows(z, "z")
+    kind, v = _variable(y)
     rows = x.shape[0]
     if v.shape[0] != rows:
         raise ValueError(f"z and y must have one row count, got {rows} and {v.shape[0]}")
@@ -157,13 +156,13 @@ class _MiRun:
         """c = _mi_check(...)"""
         self.c, self.dev, self.lib, self.st = c, dev, _lib.lib(), ops._stream()
         n, k = c["n"], c["k"]
-        Z = _to_device(c["x"], dev)
+        Z = _on_device(c["x"], dev)
         if not c["kept"].all():
             Z = Z[torch.from_numpy(c["kept"]).to(dev)].contiguous()
         self.Z, self.n, self.k, self.ld = Z, n, k, Z.shape[1]
         self.real = c["kind"] == "real"
         if self.real:
-            self.Y = _to_device(c["v"], dev)
+            self.Y = _on_device(c["v"], dev)
             self.q = self.Y.shape[1]
             self.lab = self.kk = None
         else:
@@ -212,18 +211,13 @@ class _MiRun:
         return p
 
 
-def _mi_pick(c):
-    x = c["x"]
-    return x if torch.is_tensor(x) and x.is_cuda else c.get("v")
-
-
 def mutual_information(z, y, *, n_neighbors=3, return_parts=False):
     """The kNN estimate of the mutual information of the rows of z [n, d] and y (real [n] / [n, q <= 4]: KSG; integer labels [n]:
     Ross), in nats, not clipped at 0.  return_parts=True: (I, dict) with rho2 [n] fp64, nz [n] int32 and ny [n] int32 (real y) or
     k [n], count [n] int32 (labels: each row's k_i and class size), over the kept rows, and kept, the bool mask over the rows of z
     that survived the drop of labels that occur once.  See the module docstring for the definitions."""
     c = _mi_check(z, y, n_neighbors)
-    dev = _device_of(_mi_pick(c))
+    dev = _device_of(c["x"], c.get("v"))
     with torch.cuda.device(dev):
         run = _MiRun(c, dev)
         out = torch.zeros(2, dtype=torch.float64, device=dev)
@@ -247,19 +241,10 @@ def mutual_information_permutation_test(z, y, *, n_neighbors=3, n_permutations=2
     three launches of mutual_information on a device-side gather of y; the sums are read back once per 64 permutations."""
     c = _mi_check(z, y, n_neighbors)
     n = c["n"]
-    perms = None
-    if permutations is None:
-        P = _mmd_count(n_permutations)
-    else:
-        perms = _mmd_permutation_array(permutations, n)
-        P = perms.shape[0]
-    dev = _device_of(_mi_pick(c))
+    perms, P = _given_or_count(permutations, n_permutations, n)
+    dev = _device_of(c["x"], c.get("v"))
     with torch.cuda.device(dev):
-        if perms is not None:
-            perms = perms.to(device=dev, dtype=torch.int64)
-            _mmd_check_permutations(perms)
-        else:
-            perms = mmd_permutations(n, P, seed, dev)
+        perms = _on_device_or_drawn(perms, n, P, seed, dev)
         run = _MiRun(c, dev)
         out = torch.zeros(_MI_READ, 2, dtype=torch.float64, device=dev)
         run.run(out[0])
@@ -270,8 +255,7 @@ def mutual_information_permutation_test(z, y, *, n_neighbors=3, n_permutations=2
             for p in range(count):
                 run.run(out[p], perms[p0 + p])
             null[p0: p0 + count] = run.close(out[:count].cpu().numpy())
-    pvalue = (1 + int((null >= statistic).sum())) / (1 + P)
-    return MIPermutationResult(statistic, pvalue, null)
+    return MIPermutationResult(statistic, _pvalue(statistic, null), null)
 
 
 def mi_scores_inputs(z, y, discrete_target, random_state):
@@ -300,21 +284,18 @@ def latent_mi_scores(z, y, *, discrete_target=False, n_neighbors=3, random_state
     or mutual_info_classif(z, y) (discrete_target=True: integer labels [n]) with all features continuous, including their scaling
     and their 1e-10 noise from RandomState(random_state).  Column c is handed to the kernels as a view of the scaled z (row stride
     d, one feature), so nothing is copied per column."""
-    x = _mmd_rows(z, "z")
-    if x.shape[1] < 1:
-        raise ValueError("z must have at least one feature")
-    kind, v = _hsic_variable(y)
+    x = _feature_rows(z, "z")
+    kind, v = _variable(y)
     if (kind == "labels") != bool(discrete_target):
         raise ValueError(f"discrete_target={discrete_target!r} takes {'integer labels' if discrete_target else 'a floating y'}, got {kind}")
     if kind == "real" and v.shape[1] != 1:
         raise ValueError(f"latent_mi_scores takes one real target [n], got {v.shape[1]} columns")
     if v.shape[0] != x.shape[0]:
         raise ValueError(f"z and y must have one row count, got {x.shape[0]} and {v.shape[0]}")
-    dev_pick = x if torch.is_tensor(x) and x.is_cuda else (v if kind == "real" else None)
     host = (lambda a: a.cpu().numpy() if torch.is_tensor(a) else a)
     xs, ys = mi_scores_inputs(host(x), host(v).reshape(-1), kind == "labels", random_state)
     c = _mi_check(xs, ys, n_neighbors)
-    dev = _device_of(dev_pick)
+    dev = _device_of(x, v)   # the given arrays, not their scaled host copies; labels are a host array
     with torch.cuda.device(dev):
         run = _MiRun(c, dev)
         d = xs.shape[1]

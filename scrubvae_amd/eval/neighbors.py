@@ -27,27 +27,29 @@ One pass over the n^2 (m n) distances, nothing of that size stored; n_neighbors 
 ValueError for non-finite rows and for every argument out of range, before any device work."""
 from __future__ import annotations
 
+import functools
+
 import numpy as np
 import torch
 
 from .. import _lib, ops
 from .._lib import check
-from ._device import _clock
-from .metrics import _device_of, _mmd_rows
-from .silhouette import _sil_labels
+from . import _device
+from ._device import _clock, _on_device
+from ._inputs import _feature_rows, _finite_rows, _int_labels, _is_int
 
 KNN_MAX_K = _lib.KNN_MAX_K             # the cap on n_neighbors
 _KNN_CALLS = {"knn": 0, "cross": 0}    # launches of svae_knn / svae_knn_cross by this process
 _KNN_LAST = {"work": 0, "chunks": 0}   # bytes of work and column chunks per row tile of the last run
 
+_device_of = functools.partial(_device._device_of, who="the neighbour search runs on the GPU (csrc/knn.hip); no device is available")
+
 
 def _knn_check(z, n_neighbors, group=None):
     """the argument errors, before any device work -> (fp64 rows, k, group int32 [n] numpy or None)"""
-    x = _mmd_rows(z, "z")
-    n, d = x.shape
-    if d < 1:
-        raise ValueError("z must have at least one feature")
-    if isinstance(n_neighbors, bool) or not isinstance(n_neighbors, (int, np.integer)):
+    x = _feature_rows(z, "z")
+    n = x.shape[0]
+    if not _is_int(n_neighbors):
         raise ValueError(f"n_neighbors must be an integer, got {n_neighbors!r}")
     k = int(n_neighbors)
     if k < 1:
@@ -60,7 +62,7 @@ def _knn_check(z, n_neighbors, group=None):
         raise ValueError(f"at most 2^31 - 1 rows are supported, got {n}")
     grp = None
     if group is not None:
-        _, grp, count = np.unique(_sil_labels(group, n), return_inverse=True, return_counts=True)
+        _, grp, count = np.unique(_int_labels(group, n), return_inverse=True, return_counts=True)
         grp = grp.reshape(-1).astype(np.int32)
         if n - count.max() < k:
             raise ValueError(f"group {int(count.argmax())} (in np.unique order) holds {int(count.max())} of the {n} rows: its rows keep "
@@ -75,9 +77,7 @@ def _knn_device(x, k, grp, info=None):
     n, d = x.shape
     with torch.cuda.device(dev):
         lib = _lib.lib()
-        if not torch.is_tensor(x):
-            x = torch.from_numpy(x if x.flags.writeable else x.copy())  # torch refuses to share a read-only array
-        Z = x.to(dev).contiguous()
+        Z = _on_device(x, dev)
         gd = None if grp is None else torch.from_numpy(grp).to(dev)
         nbytes = lib.svae_knn_work(n, k)
         work = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
@@ -103,7 +103,7 @@ def kneighbors(z, n_neighbors, *, group=None, return_distance=True):
 
 def _knn_cross_check(z_ref, z_query, n_neighbors):
     """the argument errors of a query set against a reference set, before any device work -> (fp64 reference rows, query rows, k)"""
-    x, q = _mmd_rows(z_ref, "z_ref"), _mmd_rows(z_query, "z_query")
+    x, q = _finite_rows(z_ref, "z_ref"), _finite_rows(z_query, "z_query")
     n, d = x.shape
     if d < 1:
         raise ValueError("z_ref must have at least one feature")
@@ -111,7 +111,7 @@ def _knn_cross_check(z_ref, z_query, n_neighbors):
         raise ValueError(f"z_query has {q.shape[1]} features, z_ref has {d}")
     if n < 1 or q.shape[0] < 1:
         raise ValueError(f"z_ref and z_query need at least one row each, got {n} and {q.shape[0]}")
-    if isinstance(n_neighbors, bool) or not isinstance(n_neighbors, (int, np.integer)):
+    if not _is_int(n_neighbors):
         raise ValueError(f"n_neighbors must be an integer, got {n_neighbors!r}")
     k = int(n_neighbors)
     if k < 1:
@@ -123,13 +123,6 @@ def _knn_cross_check(z_ref, z_query, n_neighbors):
     if n >= 2 ** 31 or q.shape[0] >= 2 ** 31:
         raise ValueError(f"at most 2^31 - 1 rows are supported, got {n} and {q.shape[0]}")
     return x, q, k
-
-
-def _rows_on(x, dev):
-    """fp64 rows (numpy or torch) as a contiguous tensor on dev"""
-    if not torch.is_tensor(x):
-        x = torch.from_numpy(x if x.flags.writeable else x.copy())  # torch refuses to share a read-only array
-    return x.to(dev).contiguous()
 
 
 def _knn_cross_device(X, Q, k):
@@ -147,9 +140,9 @@ def _knn_cross_device(X, Q, k):
 
 
 def _knn_cross(x, q, k):
-    dev = _device_of(q) if torch.is_tensor(q) and q.is_cuda else _device_of(x)
+    dev = _device_of(q, x)
     with torch.cuda.device(dev):
-        return _knn_cross_device(_rows_on(x, dev), _rows_on(q, dev), k)
+        return _knn_cross_device(_on_device(x, dev), _on_device(q, dev), k)
 
 
 def kneighbors_cross(z_ref, z_query, n_neighbors, *, return_distance=True):
@@ -178,8 +171,8 @@ def knn_transfer_labels(z_ref, labels_ref, z_query, n_neighbors, *, noise_label=
     labels of a clustering (GaussianMixture, HDBSCAN) of z_ref to new windows.  noise_label names the label that stands for "no
     cluster" (HDBSCAN's -1): reference rows that carry it still vote, so a query among noise is noise."""
     x, q, k = _knn_cross_check(z_ref, z_query, n_neighbors)
-    lab = _sil_labels(labels_ref, x.shape[0])
-    if noise_label is not None and (isinstance(noise_label, bool) or not isinstance(noise_label, (int, np.integer))):
+    lab = _int_labels(labels_ref, x.shape[0])
+    if noise_label is not None and not _is_int(noise_label):
         raise ValueError(f"noise_label must be an integer or None, got {noise_label!r}")
     _, idx = _knn_cross(x, q, k)
     return _vote(np.asarray(lab).reshape(-1)[idx.cpu().numpy().astype(np.int64)])
@@ -207,7 +200,7 @@ def knn_label_purity(z, labels, n_neighbors):
     """(the share of each row's n_neighbors neighbours that carry the row's own label [n] float64, its mean as a float): do the
     windows of one animal or class still sit next to each other?  labels [n], any integer dtype, numpy or torch."""
     x, k, _ = _knn_check(z, n_neighbors)
-    _, lab = np.unique(_sil_labels(labels, x.shape[0]), return_inverse=True)
+    _, lab = np.unique(_int_labels(labels, x.shape[0]), return_inverse=True)
     _, idx = _knn_device(x, k, None)
     labd = torch.from_numpy(lab.reshape(-1).astype(np.int64)).to(idx.device)
     same = (labd[idx.long()] == labd[:, None]).sum(1)

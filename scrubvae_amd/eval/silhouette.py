@@ -35,6 +35,7 @@ Differences from sklearn, by design:
 """
 from __future__ import annotations
 
+import functools
 from collections import namedtuple
 
 import numpy as np
@@ -42,8 +43,9 @@ import torch
 
 from .. import _lib, ops
 from .._lib import check
-from ._device import _clock
-from .metrics import _device_of, _mmd_rows
+from . import _device
+from ._device import _clock, _on_device
+from ._inputs import _feature_rows, _int_labels
 
 SIL_MAX_CLUSTERS = _lib.SIL_MAX_CLUSTERS  # the cap on the number of clusters
 _SIL_ROWS_PER_LAUNCH = 32768              # rows per svae_silhouette launch: bounds the partials (64 MB at K <= 256, 1 GB at 4096)
@@ -52,31 +54,15 @@ _SIL_LAST = {"work": 0, "ranges": 0}      # doubles of work and row ranges of th
 
 SilhouetteParts = namedtuple("SilhouetteParts", ["s", "a", "b", "nearest"])
 
-
-def _sil_labels(labels, n):
-    """labels -> a 1-D integer numpy array of length n on the host"""
-    if torch.is_tensor(labels):
-        t = labels.detach()
-        if t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
-            raise ValueError(f"labels must hold integers, got {t.dtype}")
-        lab = t.cpu().numpy()
-    else:
-        lab = np.asarray(labels)
-        if lab.dtype.kind not in "iu":
-            raise ValueError(f"labels must hold integers, got {lab.dtype}")
-    if lab.ndim != 1 or lab.shape[0] != n:
-        raise ValueError(f"labels must be [n = {n}], got shape {tuple(lab.shape)}")
-    return lab
+_device_of = functools.partial(_device._device_of, who="the silhouette runs on the GPU (csrc/silhouette.hip); no device is available")
 
 
 def _sil_check(z, labels, noise_label):
     """the argument errors, before any device work -> (fp64 rows kept, lab int32 [m] in 0..K-1, count int32 [K], cluster labels
     [K], keep: the positions of the kept rows among all n (None: all of them), n)"""
-    x = _mmd_rows(z, "z")
+    x = _feature_rows(z, "z")
     n = x.shape[0]
-    if x.shape[1] < 1:
-        raise ValueError("z must have at least one feature")
-    labels = _sil_labels(labels, n)
+    labels = _int_labels(labels, n)
     keep = None
     kept = labels
     if noise_label is not None:
@@ -111,9 +97,7 @@ def _sil_device(x, lab, count, info=None):
     K = len(count)
     with torch.cuda.device(dev):
         lib = _lib.lib()
-        if not torch.is_tensor(x):
-            x = torch.from_numpy(x if x.flags.writeable else x.copy())  # torch refuses to share a read-only array
-        Z = x.to(dev).contiguous()
+        Z = _on_device(x, dev)
         labd = torch.from_numpy(lab).to(dev)
         cnt = torch.from_numpy(count).to(dev)
         st = ops._stream()

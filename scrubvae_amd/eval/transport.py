@@ -37,7 +37,6 @@ svae_tsne_sums' fixed-order compensated sum.  Every result is bit-reproducible."
 from __future__ import annotations
 
 import functools
-import math
 import warnings
 
 import numpy as np
@@ -46,8 +45,9 @@ import torch
 from .. import _lib, ops
 from .._lib import check
 from . import _device
-from .metrics import ConvergenceWarning, _mmd_rows
-from .silhouette import _sil_labels
+from ._device import _on_device
+from ._inputs import _finite_rows, _int_labels, _is_int, _is_number
+from .metrics import ConvergenceWarning
 
 OT_MAX_COLS = _lib.OT_MAX_COLS   # columns of V per svae_ot_apply launch; wider V is handled in slices
 _KINDS = {"sqeuclidean": 0, "euclidean": 1}
@@ -60,8 +60,8 @@ _device_of = functools.partial(_device._device_of, who="optimal transport runs o
 
 # ---- arguments, before any device work --------------------------------------------------------------------------------------------
 def _number(v, name, lo_open=None, integer=False):
-    ok = not isinstance(v, bool) and isinstance(v, (int, np.integer) if integer else (int, float, np.integer, np.floating))
-    if not ok or not math.isfinite(v) or (lo_open is not None and not v > lo_open):
+    ok = _is_int(v) if integer else _is_number(v)
+    if not ok or (lo_open is not None and not v > lo_open):
         raise ValueError(f"{name} must be a finite {'integer' if integer else 'number'}" + (f" > {lo_open}" if lo_open is not None else "") +
                          f", got {v!r}")
     return int(v) if integer else float(v)
@@ -81,7 +81,7 @@ def _weights(w, n, name):
 
 
 def _ot_check(X, Y, epsilon, cost, a, b, scaling, tol, max_iter, check_every):
-    x, y = _mmd_rows(X, "X"), _mmd_rows(Y, "Y")
+    x, y = _finite_rows(X, "X"), _finite_rows(Y, "Y")
     nx, ny = x.shape[0], y.shape[0]
     if nx < 1 or ny < 1 or nx >= 1 << 26 or ny >= 1 << 26:
         raise ValueError(f"X and Y need between 1 and 2^26 - 1 rows each, got {nx} and {ny}")
@@ -103,16 +103,11 @@ def _ot_check(X, Y, epsilon, cost, a, b, scaling, tol, max_iter, check_every):
 
 
 # ---- the device side --------------------------------------------------------------------------------------------------------------
-def _on_device(t, dev):
-    """fp64 rows (numpy or torch) as a contiguous tensor on dev; torch refuses to share a read-only array"""
-    return (t if torch.is_tensor(t) else torch.from_numpy(t if t.flags.writeable else t.copy())).to(dev).contiguous()
-
-
 class _Sets:
     """the two row sets on one device with their weights, and the launches of csrc/ot.hip between them"""
 
     def __init__(self, x, y, a, b, kind, same=False):
-        self.dev = _device_of(x if torch.is_tensor(x) and x.is_cuda else y)
+        self.dev = _device_of(x, y)
         self.kind = kind
         with torch.cuda.device(self.dev):
             self.lib = _lib.lib()
@@ -275,7 +270,7 @@ class SinkhornResult:
                 f"n_iter={self.n_iter}, marginal_error={self.marginal_error:.3g}, converged={self.converged})")
 
     def _columns(self, V, n, name):
-        v = _mmd_rows(V, name)
+        v = _finite_rows(V, name)
         if v.shape[0] != n or v.shape[1] < 1:
             raise ValueError(f"{name} must be [{n}, c] with c >= 1, got shape {tuple(v.shape)}")
         return (v if torch.is_tensor(v) else torch.from_numpy(v)).to(self._sets.dev)
@@ -312,7 +307,7 @@ class SinkhornResult:
         """(ids, share [nx, K]): the share of each X row's mass that lands in each label of Y; every distinct value of labels_y [ny]
         (any integer dtype, numpy or torch) is a label, in np.unique order"""
         S = self._sets
-        ids, inv = np.unique(_sil_labels(labels_y, S.ny), return_inverse=True)
+        ids, inv = np.unique(_int_labels(labels_y, S.ny), return_inverse=True)
         with torch.cuda.device(S.dev):
             lab = torch.from_numpy(inv.reshape(-1).astype(np.int64)).to(S.dev)
             onehot = (lab[:, None] == torch.arange(len(ids), device=S.dev)[None, :]).to(torch.float64)
@@ -382,7 +377,7 @@ def transport_flow(result, labels_x, labels_y):
     that do not share rows."""
     if not isinstance(result, SinkhornResult):
         raise ValueError("result must be what sinkhorn() returned")
-    lx = _sil_labels(labels_x, result._sets.nx)
+    lx = _int_labels(labels_x, result._sets.nx)
     ids_x, inv = np.unique(lx, return_inverse=True)
     inv = inv.reshape(-1)
     ids_y, share = result.flow(labels_y)

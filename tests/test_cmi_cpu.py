@@ -167,9 +167,10 @@ def test_argument_errors_before_device_work(z, y, c, kwargs, monkeypatch):
 ])
 def test_permutation_argument_errors(kwargs, monkeypatch):
     from scrubvae_amd import _lib
+    from scrubvae_amd.eval import _permutation as PM
     from scrubvae_amd.eval import conditional_mi as CM
     from scrubvae_amd.eval import metrics as M
-    assert CM._mmd_permutation_array is M._mmd_permutation_array and CM._mmd_count is M._mmd_count   # imported, not copied
+    assert CM._given_or_count is PM._given_or_count and CM._count is PM._count   # imported, not copied
     assert CM.mmd_permutations is M.mmd_permutations
     monkeypatch.setattr(_lib, "lib", lambda: (_ for _ in ()).throw(AssertionError("library loaded")))
     with pytest.raises(ValueError):

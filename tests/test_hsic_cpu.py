@@ -162,10 +162,11 @@ def test_argument_errors_before_device_work(z, y, kwargs, monkeypatch):
 def test_permutation_errors_are_those_of_mmd_permutation_test(kwargs, monkeypatch):
     from scrubvae_amd import _lib
     from scrubvae_amd.eval import hsic_permutation_test
+    from scrubvae_amd.eval import _permutation as PM
     from scrubvae_amd.eval import independence as IN
     from scrubvae_amd.eval import metrics as M
-    assert IN._mmd_permutation_array is M._mmd_permutation_array and IN._mmd_check_permutations is M._mmd_check_permutations
-    assert IN._mmd_count is M._mmd_count and IN.mmd_permutations is M.mmd_permutations  # imported, not copied
+    assert IN._given_or_count is PM._given_or_count and IN._on_device_or_drawn is PM._on_device_or_drawn
+    assert IN._pvalue is PM._pvalue and M.mmd_permutations is PM.mmd_permutations  # imported, not copied
     monkeypatch.setattr(_lib, "lib", lambda: (_ for _ in ()).throw(AssertionError("library loaded")))
     for y in (Y4, C4):
         with pytest.raises(ValueError):
@@ -182,13 +183,13 @@ def test_bandwidth_argument_errors(monkeypatch):
 
 
 def test_variable_kinds():
-    from scrubvae_amd.eval import independence as IN
-    kind, v = IN._hsic_variable(Y4.astype(np.float32))
+    from scrubvae_amd.eval import _inputs as IN
+    kind, v = IN._variable(Y4.astype(np.float32))
     assert kind == "real" and v.dtype == np.float64 and v.shape == (6, 1)
-    kind, v = IN._hsic_variable(torch.from_numpy(np.stack([Y4, Y4], 1)))
+    kind, v = IN._variable(torch.from_numpy(np.stack([Y4, Y4], 1)))
     assert kind == "real" and v.dtype == torch.float64 and tuple(v.shape) == (6, 2)
     for c in (C4, C4.astype(np.uint8), torch.from_numpy(C4).to(torch.int32), 10 - 3 * C4):
-        kind, v = IN._hsic_variable(c)
+        kind, v = IN._variable(c)
         assert kind == "labels" and v.dtype == np.int32 and v.flags.c_contiguous
         assert np.array_equal(v[:, None] == v[None, :], C4[:, None] == C4[None, :])
 

@@ -221,10 +221,11 @@ def test_score_argument_errors_before_device_work(z, y, kwargs, monkeypatch):
 ])
 def test_permutation_errors_are_those_of_mmd_permutation_test(kwargs, monkeypatch):
     from scrubvae_amd import _lib
+    from scrubvae_amd.eval import _permutation as PM
     from scrubvae_amd.eval import metrics as M
     from scrubvae_amd.eval import mutual_info as MI
-    assert MI._mmd_permutation_array is M._mmd_permutation_array and MI._mmd_check_permutations is M._mmd_check_permutations
-    assert MI._mmd_count is M._mmd_count and MI.mmd_permutations is M.mmd_permutations  # imported, not copied
+    assert MI._given_or_count is PM._given_or_count and MI._on_device_or_drawn is PM._on_device_or_drawn
+    assert MI._pvalue is PM._pvalue and M.mmd_permutations is PM.mmd_permutations  # imported, not copied
     monkeypatch.setattr(_lib, "lib", lambda: (_ for _ in ()).throw(AssertionError("library loaded")))
     for y in (Y6, C6):
         with pytest.raises(ValueError):

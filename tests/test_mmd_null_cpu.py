@@ -67,17 +67,35 @@ def test_permutations_draw_on_the_host():
     for n, P in [(0, 3), (5, 0)]:
         with pytest.raises(ValueError):
             mmd_permutations(n, P, 0, "cpu")
+    # the front end of the permutation tests: nothing given -> the count, then exactly this draw
+    from scrubvae_amd.eval import _permutation as PM
+    perms, P = PM._given_or_count(None, 3, 5)
+    assert perms is None and P == 3
+    assert torch.equal(PM._on_device_or_drawn(perms, 5, P, 7, torch.device("cpu")), mmd_permutations(5, 3, 7, "cpu"))
 
 
 def test_permutation_rows_are_checked():
-    from scrubvae_amd.eval import metrics as M
+    from scrubvae_amd.eval import _permutation as M
     good = torch.from_numpy(draw(50, 9, seed=1))
-    M._mmd_check_permutations(good)
+    M._check_permutations(good)
     for bad_value in (int(good[5, 4]), 50, -1):  # a repeat, past the end, negative
         bad = good.clone()
         bad[5, 3] = bad_value
         with pytest.raises(ValueError, match=r"permutations\[5\]"):
-            M._mmd_check_permutations(bad)
+            M._check_permutations(bad)
+    # through the front end: a read-only int32 array comes back as the equal int64 tensor
+    given = np.stack([np.random.default_rng(s).permutation(5) for s in range(3)]).astype(np.int32)
+    given.setflags(write=False)
+    perms, P = M._given_or_count(given, 1000, 5)
+    assert P == 3 and perms.dtype == torch.int32
+    out = M._on_device_or_drawn(perms, 5, P, 0, torch.device("cpu"))
+    assert out.dtype == torch.int64 and np.array_equal(out.numpy(), given)
+    # the rows are checked in chunks of 1024: row 1025 is the first row of the second chunk
+    long = np.tile(np.arange(4), (1026, 1))
+    long[1025, 2] = 0
+    perms, P = M._given_or_count(long, 1000, 4)
+    with pytest.raises(ValueError, match=r"permutations\[1025\]"):
+        M._on_device_or_drawn(perms, 4, P, 0, torch.device("cpu"))
 
 
 XS, YS = two_sets(4, 3, 2, seed=0)
