@@ -129,16 +129,19 @@ int svae_conv_fwd_split(const svae_conv_desc* d, const float* x, const void* wsp
  * behind the conv, residual.py:88,112,146,173): bn_part[tile][2][c_out] = per-column (sum y, sum y^2) over the valid rows of
  * row tile `tile`, y = the value written (bias and, with accumulate, the previous content included) -- the layout of
  * svae_bn_stats_partial with svae_conv_fwd_stats_tiles(d) in place of svae_bn_chunks(rows); feed it to
- * svae_bn_stats_finalize / svae_bn_reduce_partials.  Removes one full read of the conv output per BatchNorm. */
+ * svae_bn_stats_finalize / svae_bn_reduce_partials.  Removes one full read of the conv output per BatchNorm.
+ * bn_pivot [c_out] (NULL: zeros): the sums are taken about it, (sum (y - p), sum (y - p)^2), as in svae_bn_stats_partial; the
+ * finalize call must be given the same pivot, and must come after this launch in stream order where it overwrites the pivot. */
 int svae_conv_fwd_stats_tiles(const svae_conv_desc* d);
 int svae_conv_fwd_split_stats(const svae_conv_desc* d, const float* x, const void* wsplit, const float* bias,
-                              float* y, int accumulate, int pieces, float* bn_part, void* stream);
+                              float* y, int accumulate, int pieces, float* bn_part, const float* bn_pivot, void* stream);
 /* The same launch for a descriptor with up2 = 1 (conv behind nn.Upsample(x2, linear): residual.py:153-170) that additionally
  * writes the upsampled operand rows it blends to up_out[batch * l_in][c_in] (each row once; ld_in == c_in) -- the tensor the
  * conv's weight gradient reads in the backward pass -- so that no separate svae_upsample2_fwd launch (one more read of x) is
  * needed.  up_out = NULL: nothing is written; bn_part as above (NULL: off). */
 int svae_conv_fwd_split_up2(const svae_conv_desc* d, const float* x, const void* wsplit, const float* bias,
-                            float* y, int accumulate, int pieces, float* bn_part, float* up_out, void* stream);
+                            float* y, int accumulate, int pieces, float* bn_part, float* up_out, const float* bn_pivot,
+                            void* stream);
 int svae_conv_dgrad_split(const svae_conv_desc* d, const float* dy, const void* wsplit, float* dx,
                           int accumulate, int pieces, void* stream);
 /* The same launch when dx is the gradient with respect to the OUTPUT of a BatchNorm1d + PReLU / Tanh stage (the `add` / `residual.1-2`
@@ -179,24 +182,28 @@ int svae_pack_input(const float* x6d, const float* root, const float* arena, flo
                     long long rows, int n_joints, int ld, void* stream);
 
 /* Train-mode BatchNorm1d statistics (residual.py:88,112,146,173): per-channel partial
- * sums over row chunks.  part [n_chunks][2][C] (sum, sum of squares); n_chunks returned by
- * svae_bn_chunks(rows). */
+ * sums over row chunks.  part [n_chunks][2][C] (sum, sum of squares) of x - pivot; n_chunks returned by
+ * svae_bn_chunks(rows).  pivot [C] (NULL: zeros) is any per-channel value near the batch mean, e.g. the running mean: each
+ * partial is an fp32 sum, so the rounding of the sum of squares scales with var + (mean - pivot)^2, and the variance
+ * E[(x-p)^2] - E[x-p]^2 keeps its relative accuracy only while |mean - pivot| is not large against the standard deviation. */
 int svae_bn_chunks(long long rows);
-int svae_bn_stats_partial(const float* x, long long rows, int C, int ld, float* part, void* stream);
+int svae_bn_stats_partial(const float* x, long long rows, int C, int ld, float* part, const float* pivot, void* stream);
 /* Finalize: sums over chunks in fixed order (fp64), `count` = rows over ALL ranks (the
  * caller all-reduces `part` reduced to [2][C] for sync-BN, see svae_bn_reduce_partials).
  * Writes scale = gamma*rstd, shift = beta-mean*scale, saves mean/rstd, updates running
- * stats with momentum (unbiased var) when running_mean != NULL. */
+ * stats with momentum (unbiased var) when running_mean != NULL.  pivot [C] (NULL: zeros) is the pivot the sums were taken
+ * about: mean = pivot + S/N, var = Q/N - (S/N)^2.  It may be running_mean itself: each channel's pivot is read before
+ * its running mean is written, by the same thread. */
 int svae_bn_reduce_partials(const float* part, int n_chunks, int C, float* sums /*[2][C]*/, void* stream);
 int svae_bn_finalize(const float* sums, double count, int C, const float* gamma, const float* beta,
                      float eps, float momentum, float* running_mean, float* running_var,
-                     float* mean, float* rstd, float* scale, float* shift, void* stream);
+                     float* mean, float* rstd, float* scale, float* shift, const float* pivot, void* stream);
 /* single-rank fast path: svae_bn_reduce_partials + svae_bn_finalize in one launch; also
  * increments *num_batches_tracked (int64, may be NULL) */
 int svae_bn_stats_finalize(const float* part, int n_chunks, double count, int C, const float* gamma,
                            const float* beta, float eps, float momentum, float* running_mean,
                            float* running_var, long long* num_batches_tracked, float* mean, float* rstd,
-                           float* scale, float* shift, void* stream);
+                           float* scale, float* shift, const float* pivot, void* stream);
 /* backward: chunk partials -> sums[2][C], plus (+)= dgamma, dbeta (from the sums) and dalpha
  * (from dalpha_part[n_parts]); any of the three may be NULL */
 int svae_bn_bwd_reduce(const float* part, int n_chunks, int C, float* sums, float* dgamma, float* dbeta,

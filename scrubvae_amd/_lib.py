@@ -102,8 +102,8 @@ SIGNATURES = {
     "svae_conv_split_weights_batched": (I, [C.POINTER(SplitTask), I, P]),
     "svae_conv_fwd_split": (I, [DP, P, P, P, P, I, I, P]),
     "svae_conv_fwd_stats_tiles": (I, [DP]),
-    "svae_conv_fwd_split_stats": (I, [DP, P, P, P, P, I, I, P, P]),
-    "svae_conv_fwd_split_up2": (I, [DP, P, P, P, P, I, I, P, P, P]),
+    "svae_conv_fwd_split_stats": (I, [DP, P, P, P, P, I, I, P, P, P]),
+    "svae_conv_fwd_split_up2": (I, [DP, P, P, P, P, I, I, P, P, P, P]),
     "svae_conv_dgrad_split": (I, [DP, P, P, P, I, I, P]),
     "svae_conv_dgrad_stats_tiles": (I, [DP, C.POINTER(I)]),
     "svae_conv_dgrad_split_bn": (I, [DP, P, P, P, I, I, C.POINTER(BnBwdFuse), P]),
@@ -112,10 +112,10 @@ SIGNATURES = {
     "svae_conv_epilogue_wide": (I, [I]),
     "svae_pack_input": (I, [P, P, C.POINTER(F), P, LL, I, I, P]),
     "svae_bn_chunks": (I, [LL]),
-    "svae_bn_stats_partial": (I, [P, LL, I, I, P, P]),
+    "svae_bn_stats_partial": (I, [P, LL, I, I, P, P, P]),
     "svae_bn_reduce_partials": (I, [P, I, I, P, P]),
-    "svae_bn_finalize": (I, [P, D, I, P, P, F, F, P, P, P, P, P, P, P]),
-    "svae_bn_stats_finalize": (I, [P, I, D, I, P, P, F, F, P, P, P, P, P, P, P, P]),
+    "svae_bn_finalize": (I, [P, D, I, P, P, F, F, P, P, P, P, P, P, P, P]),
+    "svae_bn_stats_finalize": (I, [P, I, D, I, P, P, F, F, P, P, P, P, P, P, P, P, P]),
     "svae_bn_bwd_reduce": (I, [P, I, I, P, P, P, P, P, I, I, P]),
     "svae_colsum_batched_workspace": (SZ, [C.POINTER(ColsumTask), I]),
     "svae_colsum_batched": (I, [C.POINTER(ColsumTask), I, P, SZ, I, P]),

@@ -51,7 +51,7 @@ __global__ __launch_bounds__(256) void pack_input_kernel(const float* __restrict
 constexpr int STAT_ROWS = 128;  // rows per block of the BatchNorm partial-sum kernels (512 gave only 128 blocks per layer: 1.5 TB/s)
 
 __global__ __launch_bounds__(256) void bn_stats_partial_kernel(const float* __restrict__ x, long long rows, int C, int ld,
-                                                                float* __restrict__ part) {
+                                                                float* __restrict__ part, const float* __restrict__ pivot) {
   __shared__ float red[2][16][65];
   const int c4 = threadIdx.x & 15, rl = threadIdx.x >> 4;
   const int c = blockIdx.y * 64 + c4 * 4;
@@ -59,12 +59,17 @@ __global__ __launch_bounds__(256) void bn_stats_partial_kernel(const float* __re
   long long r1 = r0 + STAT_ROWS;
   if (r1 > rows) r1 = rows;
   float4 s = make_float4(0.f, 0.f, 0.f, 0.f), q = s;
-  if (c < C)
+  if (c < C) {
+    // sums of x - pivot: a chunk's fp32 sum of squares rounds at the size of var + (mean - pivot)^2, not of var + mean^2
+    float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (pivot != nullptr) p = make_float4(pivot[c], pivot[c + 1], pivot[c + 2], pivot[c + 3]);
     for (long long r = r0 + rl; r < r1; r += 16) {
-      const float4 v = ld4(x + r * ld + c);
+      float4 v = ld4(x + r * ld + c);
+      v.x -= p.x; v.y -= p.y; v.z -= p.z; v.w -= p.w;
       s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
       q.x += v.x * v.x; q.y += v.y * v.y; q.z += v.z * v.z; q.w += v.w * v.w;
     }
+  }
   red[0][rl][c4 * 4 + 0] = s.x; red[0][rl][c4 * 4 + 1] = s.y; red[0][rl][c4 * 4 + 2] = s.z; red[0][rl][c4 * 4 + 3] = s.w;
   red[1][rl][c4 * 4 + 0] = q.x; red[1][rl][c4 * 4 + 1] = q.y; red[1][rl][c4 * 4 + 2] = q.z; red[1][rl][c4 * 4 + 3] = q.w;
   __syncthreads();
@@ -90,11 +95,14 @@ __global__ void reduce_partials_kernel(const float* __restrict__ part, int chunk
 
 __global__ void bn_finalize_kernel(const float* __restrict__ sums, double count, int C, const float* __restrict__ gamma,
                                    const float* __restrict__ beta, float eps, float momentum, float* running_mean,
-                                   float* running_var, float* mean_o, float* rstd_o, float* scale, float* shift) {
+                                   float* running_var, float* mean_o, float* rstd_o, float* scale, float* shift, const float* pivot) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
-  const double mean = (double)sums[c] / count;
-  double var = (double)sums[C + c] / count - mean * mean;
+  // the sums are those of x - pivot (pivot may alias running_mean: read here, before this thread writes the channel below)
+  const double piv = pivot != nullptr ? (double)pivot[c] : 0.0;
+  const double dm = (double)sums[c] / count;
+  const double mean = piv + dm;
+  double var = (double)sums[C + c] / count - dm * dm;
   if (var < 0.0) var = 0.0;
   const float rstd = (float)(1.0 / sqrt(var + (double)eps));
   const float g = gamma[c], b = beta[c];
@@ -140,14 +148,16 @@ __device__ __forceinline__ bool chunk_sums(const float* __restrict__ part, int c
 __global__ __launch_bounds__(256) void bn_stats_finalize_kernel(const float* __restrict__ part, int chunks, double count, int C, int cpb,
                                          const float* __restrict__ gamma, const float* __restrict__ beta, float eps, float momentum,
                                          float* running_mean, float* running_var, long long* num_batches_tracked, float* mean_o,
-                                         float* rstd_o, float* scale, float* shift) {
+                                         float* rstd_o, float* scale, float* shift, const float* pivot) {
   __shared__ double red[2][FIN_THREADS];
   if (blockIdx.x == 0 && threadIdx.x == 0 && num_batches_tracked != nullptr) *num_batches_tracked += 1;
   double s0, s1;
   int c;
   if (!chunk_sums(part, chunks, C, cpb, s0, s1, c, red)) return;
-  const double mean = s0 / count;
-  double var = s1 / count - mean * mean;
+  const double piv = pivot != nullptr ? (double)pivot[c] : 0.0;  // may alias running_mean: read before the write below
+  const double dm = s0 / count;
+  const double mean = piv + dm;
+  double var = s1 / count - dm * dm;
   if (var < 0.0) var = 0.0;
   const float rstd = (float)(1.0 / sqrt(var + (double)eps));
   const float g = gamma[c], b = beta[c];
@@ -854,10 +864,11 @@ extern "C" int svae_pack_input(const float* x6d, const float* root, const float*
 
 extern "C" int svae_bn_chunks(long long rows) { return (int)((rows + STAT_ROWS - 1) / STAT_ROWS); }
 
-extern "C" int svae_bn_stats_partial(const float* x, long long rows, int C, int ld, float* part, void* stream) {
+extern "C" int svae_bn_stats_partial(const float* x, long long rows, int C, int ld, float* part, const float* pivot, void* stream) {
   SVAE_REQUIRE(x && part && rows > 0, SVAE_ERR_ARG, "bn_stats: null pointer");
   SVAE_REQUIRE(C % 4 == 0 && ld % 4 == 0 && aligned16(x), SVAE_ERR_ALIGN, "bn_stats: C, ld must be multiples of 4");
-  hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(svae_bn_chunks(rows), (C + 63) / 64), dim3(256), 0, ST(stream), x, rows, C, ld, part);
+  hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(svae_bn_chunks(rows), (C + 63) / 64), dim3(256), 0, ST(stream), x, rows, C, ld, part,
+                     pivot);
   return check_launch("bn_stats_partial");
 }
 
@@ -869,10 +880,10 @@ extern "C" int svae_bn_reduce_partials(const float* part, int n_chunks, int C, f
 
 extern "C" int svae_bn_finalize(const float* sums, double count, int C, const float* gamma, const float* beta, float eps,
                                 float momentum, float* running_mean, float* running_var, float* mean, float* rstd,
-                                float* scale, float* shift, void* stream) {
+                                float* scale, float* shift, const float* pivot, void* stream) {
   SVAE_REQUIRE(sums && gamma && beta && mean && rstd && scale && shift && count > 0, SVAE_ERR_ARG, "bn_finalize: bad args");
   hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 127) / 128), dim3(128), 0, ST(stream), sums, count, C, gamma, beta, eps,
-                     momentum, running_mean, running_var, mean, rstd, scale, shift);
+                     momentum, running_mean, running_var, mean, rstd, scale, shift, pivot);
   return check_launch("bn_finalize");
 }
 
@@ -1081,12 +1092,13 @@ extern "C" int svae_double_softmax_ce_sum(const float* logits, int ld, int rows,
 extern "C" int svae_bn_stats_finalize(const float* part, int n_chunks, double count, int C, const float* gamma,
                                       const float* beta, float eps, float momentum, float* running_mean, float* running_var,
                                       long long* num_batches_tracked, float* mean, float* rstd, float* scale, float* shift,
-                                      void* stream) {
+                                      const float* pivot, void* stream) {
   SVAE_REQUIRE(part && gamma && beta && mean && rstd && scale && shift && count > 0 && n_chunks > 0, SVAE_ERR_ARG,
                "bn_stats_finalize: bad args");
   const int cpb = fin_cpb(C);
   hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3((C + cpb - 1) / cpb), dim3(256), 0, ST(stream), part, n_chunks, count, C, cpb, gamma,
-                     beta, eps, momentum, running_mean, running_var, num_batches_tracked, mean, rstd, scale, shift);
+                     beta, eps, momentum, running_mean, running_var, num_batches_tracked, mean, rstd, scale, shift,
+                     pivot);
   return check_launch("bn_stats_finalize");
 }
 

@@ -1062,20 +1062,21 @@ extern "C" int svae_conv_fwd_stats_tiles(const svae_conv_desc* d) {
 
 extern "C" int svae_conv_fwd_split(const svae_conv_desc* d, const float* x, const void* wsplit, const float* bias, float* y,
                                    int accumulate, int pieces, void* stream) {
-  return svae_conv_fwd_split_stats(d, x, wsplit, bias, y, accumulate, pieces, nullptr, stream);
+  return svae_conv_fwd_split_stats(d, x, wsplit, bias, y, accumulate, pieces, nullptr, nullptr, stream);
 }
 
 extern "C" int svae_conv_fwd_split_stats(const svae_conv_desc* d, const float* x, const void* wsplit, const float* bias, float* y,
-                                         int accumulate, int pieces, float* bn_part, void* stream) {
-  return svae_conv_fwd_split_up2(d, x, wsplit, bias, y, accumulate, pieces, bn_part, nullptr, stream);
+                                         int accumulate, int pieces, float* bn_part, const float* bn_pivot, void* stream) {
+  return svae_conv_fwd_split_up2(d, x, wsplit, bias, y, accumulate, pieces, bn_part, nullptr, bn_pivot, stream);
 }
 
 extern "C" int svae_conv_fwd_split_up2(const svae_conv_desc* d, const float* x, const void* wsplit, const float* bias, float* y,
-                                       int accumulate, int pieces, float* bn_part, float* up_out, void* stream) {
+                                       int accumulate, int pieces, float* bn_part, float* up_out, const float* bn_pivot, void* stream) {
   if (int e = validate(d)) return e;
   SVAE_REQUIRE(up_out == nullptr || (d->up2 && aligned16(up_out) && d->ld_in == d->c_in), SVAE_ERR_ARG,
                "conv_fwd_split_up2: up_out needs an up2 descriptor with ld_in == c_in and a 16-byte aligned buffer");
   SVAE_REQUIRE(x && wsplit && y, SVAE_ERR_ARG, "conv_fwd_split: null pointer");
+  SVAE_REQUIRE(bn_pivot == nullptr || bn_part != nullptr, SVAE_ERR_ARG, "conv_fwd_split: bn_pivot without bn_part");
   SVAE_REQUIRE(aligned16(x) && aligned16(wsplit) && aligned16(y), SVAE_ERR_ALIGN, "conv_fwd_split: pointers must be 16-byte aligned");
   SVAE_REQUIRE((pieces >= 1 && pieces <= 3) || pieces == SVAE_PIECES_F16X2, SVAE_ERR_ARG, "conv_fwd_split: pieces %d not in 1..3 / 22", pieces);
   SplitGatherArgs sa;
@@ -1089,6 +1090,7 @@ extern "C" int svae_conv_fwd_split_up2(const svae_conv_desc* d, const float* x, 
   g.A = x; g.bias = bias; g.C = y;
   g.accumulate = accumulate;
   g.stats = bn_part;
+  g.bn_pivot = bn_pivot;
   sa.up_out = up_out;
   plan_for_kind(g, d, 0);
   return launch_split_gather(sa, (hipStream_t)stream, d->tile[0], pieces);

@@ -31,7 +31,8 @@ struct GatherArgs {
   int ksplit;
   float* slab;
   // split-bf16 gather kernels: per-row-tile BatchNorm sums of the written values, [row tiles][2][N] (NULL: off).
-  // bn_x == NULL: forward statistics (sum v, sum v^2).  bn_x != NULL: the launch writes the gradient dy with respect to the
+  // bn_x == NULL: forward statistics (sum (v - p), sum (v - p)^2) about the per-column pivot p = bn_pivot (NULL: 0; the fp32
+  // rounding of the tile's sum of squares then scales with var + (mean - p)^2 instead of var + mean^2).  bn_x != NULL: the launch writes the gradient dy with respect to the
   // OUTPUT of a BatchNorm + PReLU / tanh stage whose saved input is bn_x (same row layout as C): the sums are the backward's
   // (sum du, sum du * xhat), du = dy * act'(bn_x * scale + shift), xhat = (bn_x - mean) * rstd; scale / shift / mean may be NULL
   // (bare activation); bn_alpha == NULL = tanh; bn_dalpha[blockIdx.x * gridDim.y + blockIdx.y] = sum over the tile of dy * u on
@@ -44,6 +45,7 @@ struct GatherArgs {
   const float* bn_rstd;
   const float* bn_alpha;
   float* bn_dalpha;
+  const float* bn_pivot;
   // split-bf16 gather kernels: 1 = the epilogue moves C (and the old C / bn_x it reads) in 16-byte pieces through an LDS
   // transposition where alignment allows (tile_epilogue, split_gather.h); 0 = one dword per accumulator register.  Same values.
   int wide_epi;

@@ -787,6 +787,8 @@ __device__ __forceinline__ void tile_epilogue16(const GatherArgs& g, f32x4v (&ac
     if (bwd) {
       if (g.bn_scale) { sc = g.bn_scale[col]; sh = g.bn_shift[col]; }
       if (g.bn_mean) { mu = g.bn_mean[col]; rs = g.bn_rstd[col]; }
+    } else if (g.bn_pivot) {
+      mu = g.bn_pivot[col];  // forward: the sums are taken about the column's pivot
     }
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb) {
@@ -808,8 +810,9 @@ __device__ __forceinline__ void tile_epilogue16(const GatherArgs& g, f32x4v (&ac
             cs[nb] += du;
             cq[nb] += du * (x - mu) * rs;
           } else {
-            cs[nb] += v;
-            cq[nb] += v * v;
+            const float d = v - mu;
+            cs[nb] += d;
+            cq[nb] += d * d;
           }
         }
       }

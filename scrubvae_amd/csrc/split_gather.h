@@ -18,7 +18,8 @@ struct SplitGatherArgs {
   float* up_out;              // g.up: where the upsampled operand rows go as a by-product ([rowsA][ldA], NULL: nowhere)
 };
 
-// One element's share of the epilogue's sums, with every rounding pinned: u = fma(x, scale, shift), 1 - t^2 = fma(-t, t, 1) and
+// One element's share of the epilogue's sums, with every rounding pinned (forward: `mu` carries the column's pivot, and the sums
+// are those of v - pivot; a pivot of 0 leaves v as it is): u = fma(x, scale, shift), 1 - t^2 = fma(-t, t, 1) and
 // the fp64 slope term are fused, while sum v^2 and sum du * xhat are a ROUNDED product added to the sum.  That is what every
 // instance of these kernels computed while the choice was the compiler's (it pairs (sum, sum of squares) into a packed add, which
 // keeps the multiply apart); pinned, because the two paths of one instance would otherwise be free to round differently.
@@ -34,8 +35,9 @@ __device__ __forceinline__ void epilogue_sums(float v, float x, bool bwd, bool t
     const float p = du * (x - mu) * rs;
     cq += p;
   } else {
-    cs += v;
-    const float p = v * v;
+    const float d = v - mu;
+    cs += d;
+    const float p = d * d;
     cq += p;
   }
 }
@@ -47,7 +49,8 @@ __device__ __forceinline__ void wave_lds_turn() {  // orders this wave's LDS wri
 
 // ---- epilogue shared by the gather kernels: C (+)= acc + bias, and -- when g.stats != NULL -- the BatchNorm batch statistics of
 // the values just written (reference: nn.BatchNorm1d in train mode right behind the conv, residual.py:88,112,146,173): per-column
-// (sum v, sum v^2) over the tile's valid rows go to stats[blockIdx.x][2][N], the layout bn_stats_partial writes per 128-row chunk,
+// (sum (v - p), sum (v - p)^2) over the tile's valid rows, p = g.bn_pivot[column] (NULL: 0), go to stats[blockIdx.x][2][N], the
+// layout bn_stats_partial writes per 128-row chunk,
 // so the finalize kernel sums row tiles instead of chunks and the separate statistics pass over the conv output disappears.
 // Fixed summation order (lane rows, the two half-waves, then the WR row-waves): bit-reproducible.
 //
@@ -92,6 +95,8 @@ __device__ __forceinline__ void tile_epilogue(const GatherArgs& g, f32x16 (&acc)
       if (bwd && col_ok) {
         if (g.bn_scale) { sc = g.bn_scale[col]; sh = g.bn_shift[col]; }
         if (g.bn_mean) { mu = g.bn_mean[col]; rs = g.bn_rstd[col]; }
+      } else if (col_ok && g.bn_pivot) {
+        mu = g.bn_pivot[col];
       }
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) {
@@ -152,6 +157,8 @@ __device__ __forceinline__ void tile_epilogue(const GatherArgs& g, f32x16 (&acc)
       if (bwd) {
         if (g.bn_scale) { sc = g.bn_scale[col]; sh = g.bn_shift[col]; }
         if (g.bn_mean) { mu = g.bn_mean[col]; rs = g.bn_rstd[col]; }
+      } else if (g.bn_pivot) {
+        mu = g.bn_pivot[col];
       }
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) {

@@ -63,6 +63,7 @@ def model(model_config, load_model, epoch, disentangle_config, n_keypts, directi
         disentangle_keys=disentangle_config.get("features"), conditional_keys=conditional_keys,
         arena_size=arena_size, kinematic_tree=kinematic_tree, prior=model_config.get("prior", "gaussian") or "gaussian",
         ch=model_config["channel"], discrete_classes=discrete_classes, device=device)
+    vae.bn_pivot = bool(model_config.get("bn_pivot", False))  # BatchNorm statistics summed about the running mean (ResVAE.bn_pivot)
     if verbose > 0:
         print(vae)
     if load_model is not None:

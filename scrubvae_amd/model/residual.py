@@ -220,6 +220,12 @@ class ResVAE(nn.Module):
         self.world_size, self.rank, self.process_group = 1, 0, None
         self.bucket_min_bytes = 4 << 20  # smallest encoder gradient bucket worth its own all-reduce (xGMI: few, large)
         self.sync_bn = True
+        # Train-mode BatchNorm statistics summed about the layer's running mean (see _bn_act) instead of about zero: keeps the batch
+        # variance accurate for channels whose mean is several standard deviations from zero.  Off by default: with it on a
+        # train-mode forward depends on the running statistics it finds, so two forwards of one batch in a row differ in the last
+        # bits (and, until the running mean has followed the batch mean, by the un-pivoted sums' own error), and a run no longer
+        # reproduces the numbers of a run without it.  get.model sets it from the model config's `bn_pivot` key.
+        self.bn_pivot = False
         self.shuffle_seed, self._shuffle_draws = 0, 0  # shared-seed global permutation of the adversarial shuffle (N > 1)
         # bench.py: HIP events (on the main stream) around every point where the main chain waits for a collective -- the
         # sync-BatchNorm statistics and the tail of the gradient exchange; what they bracket is the EXPOSED communication time
@@ -642,16 +648,18 @@ class ResVAE(nn.Module):
             return dist.all_reduce(t, group=self.process_group, async_op=True)
 
     # ------------------------------------------------------------------ BN + PReLU stage
-    def _conv_fwd_bn(self, cv, x, p, y, accumulate=False):
-        """Conv forward whose output feeds a train-mode BatchNorm: where the conv runs a split-bf16 kernel the per-tile
-        (sum, sum of squares) of the output come out of the GEMM epilogue.  Returns (part [tiles, 2, Cp], tiles) for _bn_act,
-        or None (eval mode / fp32 kernel: _bn_act makes its own statistics pass)."""
+    def _conv_fwd_bn(self, cv, x, p, y, bn: BatchNormP, accumulate=False):
+        """Conv forward whose output feeds the train-mode BatchNorm `bn`: where the conv runs a split-bf16 kernel the per-tile
+        (sum, sum of squares) of the output come out of the GEMM epilogue -- with self.bn_pivot taken about bn.running_mean, like
+        the statistics pass of _bn_act (the launch reads the pivot on the main stream, ahead of the finalize that updates it
+        there).  Returns (part [tiles, 2, Cp], tiles) for _bn_act, or None (eval mode / fp32 kernel: _bn_act makes its own
+        statistics pass)."""
         if self.training:
             cv.tune_fwd(x, p.weight, p.bias)
             n = cv.stats_tiles()
             if n > 0:
                 part = self._buf(f"bn.tpart.{n}.{cv.c_out_p}", (n, 2, cv.c_out_p))
-                cv.fwd(x, p.weight, p.bias, y, accumulate=accumulate, stats=part)
+                cv.fwd(x, p.weight, p.bias, y, accumulate=accumulate, stats=part, pivot=bn.running_mean if self.bn_pivot else None)
                 return part, n
         cv.fwd(x, p.weight, p.bias, y, accumulate=accumulate)
         return None
@@ -662,22 +670,26 @@ class ResVAE(nn.Module):
         if self.training:
             sums = self._buf(tag + ".sums", (2, Cp))
             mean, rstd = self._buf(tag + ".mean", (Cp,)), self._buf(tag + ".rstd", (Cp,))
+            # The (sum, sum of squares) partials are fp32: taken about a pivot near the batch mean they keep the variance's
+            # accuracy when |mean| is large against std.  The running mean is finite from the first step, the same on every
+            # rank under sync-BN and checkpointed (a resumed run keeps its bits); the .mean buffer above starts uninitialised.
+            pivot = bn.running_mean if self.bn_pivot else None  # (the same choice as _conv_fwd_bn made for `stats`)
             if stats is not None:  # statistics came out of the producing GEMM's epilogue
                 part, nch = stats
             else:
                 nch = ops.bn_chunks(rows)
                 part = self._buf(f"bn.part.{nch}.{Cp}", (nch, 2, Cp))
-                ops.bn_stats_partial(x, rows, Cp, Cp, part)
+                ops.bn_stats_partial(x, rows, Cp, Cp, part, pivot)
             if self.world_size > 1 and self.sync_bn:
                 ops.bn_reduce_partials(part, nch, Cp, sums)
                 with self._comm_bracket("bn"):
                     self._allreduce(sums)
                 ops.bn_finalize(sums, rows * self.world_size, Cp, bn.weight, bn.bias, bn.eps, bn.momentum, bn.running_mean,
-                                bn.running_var, mean, rstd, scale, shift)
+                                bn.running_var, mean, rstd, scale, shift, pivot)
                 bn.num_batches_tracked.add_(1)
             else:  # one launch: chunk reduction + finalize + running stats + num_batches_tracked
                 ops.bn_stats_finalize(part, nch, rows, Cp, bn.weight, bn.bias, bn.eps, bn.momentum, bn.running_mean,
-                                      bn.running_var, bn.num_batches_tracked, mean, rstd, scale, shift)
+                                      bn.running_var, bn.num_batches_tracked, mean, rstd, scale, shift, pivot)
         else:
             ops.bn_eval_coeffs(Cp, bn.weight, bn.bias, bn.eps, bn.running_mean, bn.running_var, scale, shift)
         ops.affine_prelu_fwd(x, scale, shift, act.weight, out, rows, Cp, Cp)
@@ -786,11 +798,11 @@ class ResVAE(nn.Module):
             cvs = self._conv(t + ".sk", blk.skip, B, L)
             self._fork(lambda: cvs.fwd(a, blk.skip.weight, blk.skip.bias, s))
             r0 = self._buf(t + ".r0", (B * Lo, cv0.c_out_p))
-            st1 = self._conv_fwd_bn(cv0, a, conv0, r0)
+            st1 = self._conv_fwd_bn(cv0, a, conv0, r0, bn1)
             r0a = self._buf(t + ".r0a", (B * Lo, cv0.c_out_p))
             self._bn_act(t + ".bn1", r0, bn1, act1, B * Lo, r0a, st1)
             self._join_side(1)
-            st2 = self._conv_fwd_bn(cv3, r0a, conv3, s, accumulate=True)  # statistics of skip + residual: the sum is what it writes
+            st2 = self._conv_fwd_bn(cv3, r0a, conv3, s, blk.add[0], accumulate=True)  # statistics of skip + residual: the sum is what it writes
             a2 = self._buf(t + ".a", (B * Lo, cv3.c_out_p))
             self._bn_act(t + ".bn2", s, blk.add[0], blk.add[1], B * Lo, a2, st2)
             a, L = a2, Lo
@@ -885,11 +897,11 @@ class ResVAE(nn.Module):
 
             self._fork(skip_branch)  # upsample + skip conv on the side stream
             t0 = self._buf(t + ".t0", (B * L, cv1.c_out_p))
-            st1 = self._conv_fwd_bn(cv1, d, ct1, t0)
+            st1 = self._conv_fwd_bn(cv1, d, ct1, t0, bn1)
             t0a = self._buf(t + ".t0a", (B * L, cv1.c_out_p))
             self._bn_act(t + ".bn1", t0, bn1, act1, B * L, t0a, st1)
             self._join_side(1)
-            st2 = self._conv_fwd_bn(cv2, t0a, ct2, s, accumulate=True)
+            st2 = self._conv_fwd_bn(cv2, t0a, ct2, s, blk.add[0], accumulate=True)
             d2 = self._buf(t + ".a", (B * Lo, cv2.c_out_p))
             self._bn_act(t + ".bn2", s, blk.add[0], blk.add[1], B * Lo, d2, st2)
             d, L = d2, Lo

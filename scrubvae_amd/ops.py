@@ -459,16 +459,16 @@ class Conv:
             n = self.__dict__["_stats_tiles"] = int(_lib.lib().svae_conv_fwd_stats_tiles(self._dref("fwd")))
         return n
 
-    def _launch_fwd(self, x, w, bias, y, acc, stats=None, up_out=None):
+    def _launch_fwd(self, x, w, bias, y, acc, stats=None, up_out=None, pivot=None):
         kp = self._kind_pieces("fwd")
         if kp and self.up2:
             return check(_lib.lib().svae_conv_fwd_split_up2(self._dref("fwd"), _p(x), _p(self.split_weights(w)), _p(bias), _p(y),
-                                                             acc, kp, _p(stats), _p(up_out), _stream()), "conv_fwd_split_up2")
+                                                             acc, kp, _p(stats), _p(up_out), _p(pivot), _stream()), "conv_fwd_split_up2")
         if up_out is not None:
             raise RuntimeError("conv_fwd: up_out is the by-product of an up2 conv's split-precision forward")
         if kp:
             return check(_lib.lib().svae_conv_fwd_split_stats(self._dref("fwd"), _p(x), _p(self.split_weights(w)), _p(bias), _p(y),
-                                                               acc, kp, _p(stats), _stream()), "conv_fwd_split")
+                                                               acc, kp, _p(stats), _p(pivot), _stream()), "conv_fwd_split")
         if stats is not None:
             raise RuntimeError("conv_fwd: fused BatchNorm statistics need a split-bf16 forward kernel (check stats_tiles())")
         ws = self._splitk_ws(0, x.device)
@@ -517,11 +517,12 @@ class Conv:
             scratch = torch.empty(self.batch * self.l_out * self.desc.ld_out + 16, device=x.device)
             self._tune("fwd", lambda: self._launch_fwd(x, w, bias, scratch, 0))
 
-    def fwd(self, x, w, bias, y, accumulate=False, stats=None, up_out=None):
-        """stats: [stats_tiles()][2][c_out_p] buffer for the fused BatchNorm statistics of y (None: off);
+    def fwd(self, x, w, bias, y, accumulate=False, stats=None, up_out=None, pivot=None):
+        """stats: [stats_tiles()][2][c_out_p] buffer for the fused BatchNorm statistics of y (None: off), taken about the
+        per-channel pivot [c_out_p] (None: zeros; hand the same pivot to bn_finalize / bn_stats_finalize);
         up_out (up2 convs): [batch * l_in, c_in_p] buffer that receives the upsampled input rows as a by-product (None: off)"""
         self.tune_fwd(x, w, bias)
-        _timed("fwd", self, self.c_out_p, lambda: self._launch_fwd(x, w, bias, y, int(accumulate), stats, up_out))
+        _timed("fwd", self, self.c_out_p, lambda: self._launch_fwd(x, w, bias, y, int(accumulate), stats, up_out, pivot))
         return y
 
     def tune_dgrad(self, dy, w):
@@ -612,22 +613,25 @@ def bn_chunks(rows):
     return int(_lib.lib().svae_bn_chunks(rows))
 
 
-def bn_stats_partial(x, rows, Cp, ld, part):
-    check(_lib.lib().svae_bn_stats_partial(_p(x), rows, Cp, ld, _p(part), _stream()), "bn_stats_partial")
+def bn_stats_partial(x, rows, Cp, ld, part, pivot=None):
+    """part [chunks, 2, Cp] = per-chunk (sum, sum of squares) of x - pivot (pivot [Cp], None: zeros)"""
+    check(_lib.lib().svae_bn_stats_partial(_p(x), rows, Cp, ld, _p(part), _p(pivot), _stream()), "bn_stats_partial")
 
 
 def bn_reduce_partials(part, n_chunks, Cp, sums):
     check(_lib.lib().svae_bn_reduce_partials(_p(part), n_chunks, Cp, _p(sums), _stream()), "bn_reduce_partials")
 
 
-def bn_finalize(sums, count, Cp, gamma, beta, eps, momentum, rmean, rvar, mean, rstd, scale, shift):
+def bn_finalize(sums, count, Cp, gamma, beta, eps, momentum, rmean, rvar, mean, rstd, scale, shift, pivot=None):
+    """pivot: what the sums were taken about (may be rmean itself: each channel's pivot is read before its running mean is written)"""
     check(_lib.lib().svae_bn_finalize(_p(sums), float(count), Cp, _p(gamma), _p(beta), eps, momentum, _p(rmean), _p(rvar),
-                                      _p(mean), _p(rstd), _p(scale), _p(shift), _stream()), "bn_finalize")
+                                      _p(mean), _p(rstd), _p(scale), _p(shift), _p(pivot), _stream()), "bn_finalize")
 
 
-def bn_stats_finalize(part, n_chunks, count, Cp, gamma, beta, eps, momentum, rmean, rvar, nbt, mean, rstd, scale, shift):
+def bn_stats_finalize(part, n_chunks, count, Cp, gamma, beta, eps, momentum, rmean, rvar, nbt, mean, rstd, scale, shift, pivot=None):
     check(_lib.lib().svae_bn_stats_finalize(_p(part), n_chunks, float(count), Cp, _p(gamma), _p(beta), eps, momentum, _p(rmean),
-                                            _p(rvar), _p(nbt), _p(mean), _p(rstd), _p(scale), _p(shift), _stream()), "bn_stats_finalize")
+                                            _p(rvar), _p(nbt), _p(mean), _p(rstd), _p(scale), _p(shift), _p(pivot), _stream()),
+          "bn_stats_finalize")
 
 
 def bn_bwd_reduce(part, n_chunks, Cp, sums, dgamma, dbeta, dalpha, dalpha_part, n_parts, accumulate):
